@@ -3,8 +3,24 @@
 fused HIP path-tracing loop on BASELINE.json configs[1] (C2): Scene/cbox,
 1024x1024 per GPU, 8 bounces, diffuse-only BRDF.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N       (one process per GPU)
+
+A plain run does what the headline needs and no more: scene upload, the
+launch-plan pick, W warmup frames, the K timed frames, the output dump when
+--dump-outputs is given, and the result line (metric, value, unit, ms_per_step,
+the plan in config).  Everything under "Also reported" below, the cache-off
+timing, the host-dump timing and, at N > 1, the image reduce and the
+strong-scaling legs are measured only with --full, in runs of their own after
+the headline.
+
+--dump-outputs DIR writes what the timed call left in the image state it was
+given, as a caller of render_frames receives it: DIR/hist.npy (pixels x 4
+float32, the accumulated mean), DIR/count.npy and DIR/seeds.npy (float64: the
+sample counts and the uint32 seed chain, exact), rank 0's state.  Seeds, scene
+and camera are fixed, and every launch plan gives the same bits, so two runs of
+one command write the same arrays.  An image whose arrays pass 64 MB is dumped
+as a fixed, seeded sample of its pixels, with their indices in DIR/pixels.npy.
 
 A step = one frame: every pixel of the image traces one sample of up to 8
 bounces and is accumulated (OpenCL::update + ColorOut once).  The path
@@ -13,7 +29,7 @@ ranks, no data-path collective), so at N > 1 the headline is weak scaling:
 each rank renders a 1024x1024 share of a 1024 x 1024N image — the C2 config
 per GPU — and value = all ranks' samples / the slowest rank's time.  The
 strong-scaled rate (the fixed 1024x1024 image striped over the ranks) is
-timed after it and reported under "strong_scaling" (C4, a fixed 1920x1080
+timed after it with --full and reported under "strong_scaling" (C4, a fixed 1920x1080
 image tile-sharded across the GPUs, is strong-scaled as its config says).
 No collective runs inside the timed region.  The timed region
 is bracketed by barrier + synchronize and the max over ranks is reported.
@@ -21,7 +37,7 @@ Scene data, seeds and accumulators are resident in HBM before timing starts.
 The timed call computes its own primary hits (k_primary, then k_render reads
 them at every frame start): nothing the warmup computed is reused.
 
-Also reported (rank 0; cpu_baseline at N=1 only):
+Also reported with --full (rank 0; cpu_baseline at N=1 only):
   roofline     — the hot kernel k_render against HBM (bound "hbm", the
                  contract's roofline): traffic = memory-side bytes per launch
                  (rocprofv3 FETCH_SIZE x the calibrated scale + WRITE_SIZE of
@@ -214,6 +230,35 @@ def load_profile(workload, steps):
         return None
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # --dump-outputs: bytes written at most
+DUMP_BYTES_PER_PIXEL = 16 + 8 + 8  # hist 4 x float32, count and seeds as float64
+
+
+def dump_pixels(n_pixels, budget=DUMP_BUDGET):
+    """The pixels --dump-outputs writes: None (all of them) when the arrays
+    fit in the budget, else a fixed, seeded, sorted sample of as many as fit
+    (their index array, float64, counts against the budget too)."""
+    if n_pixels * DUMP_BYTES_PER_PIXEL <= budget:
+        return None
+    keep = budget // (DUMP_BYTES_PER_PIXEL + 8)
+    return np.sort(np.random.default_rng(20240229).choice(n_pixels, size=keep, replace=False))
+
+
+def dump_outputs(path, st, budget=DUMP_BUDGET):
+    """--dump-outputs: the image state the timed call returned to its caller
+    (hist, count, seeds), as DIR/<name>.npy in float32 / float64."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"hist": st.hist.cpu().numpy().astype(np.float32, copy=False),
+              "count": st.count.cpu().numpy().astype(np.float64),
+              "seeds": st.seeds_np().astype(np.float64)}
+    px = dump_pixels(st.width * st.height, budget)
+    if px is not None:
+        arrays = {k: v[px] for k, v in arrays.items()}
+        arrays["pixels"] = px.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 ATTEMPT = 1 << 30  # accumulate every frame (the reference's MAX_ATTEMPT cap never binds here)
 
 
@@ -342,7 +387,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what the line reports beside it: the cache-off and "
+                         "host-dump timings, the counting replay and roofline, the CPU baseline and, at N > 1, "
+                         "the image reduce and the strong-scaling legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image state the timed call left (hist, count, seeds) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--frames-per-launch", type=int, default=0,
                     help="frames per pixel block; 0 = the library's load-balance choice")
     ap.add_argument("--workload", default="C2", choices=sorted(WORKLOADS))
@@ -350,7 +402,7 @@ def main():
                     help="k_render leaf-test schedule; auto times both before the warmup (untimed)")
     ap.add_argument("--no-strong", action="store_true", help="N > 1: skip the strong-scaling legs")
     ap.add_argument("--no-c4-leg", action="store_true", help="N > 1, C2: skip C4's strong-scaling leg")
-    ap.add_argument("--no-cache-off", action="store_true", help="skip the primary-cache-off timing")
+    ap.add_argument("--no-cache-off", action="store_true", help="--full: skip the primary-cache-off timing")
     ap.add_argument("--shade-threshold", type=int, default=0,
                     help="k_render S-phase threshold (mcpt_tuning.shade_threshold); 0: tuned with the schedule "
                          "when --schedule is auto, else the default")
@@ -426,6 +478,46 @@ def main():
 
     elapsed, rank_s = timed_render(rnd, dsc, cam, st, args.steps, args.warmup, kw, ws, shared, per_rank=True)
     kst = rnd.stats()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st)
+    fpb = kst["frames_per_block"]
+    search_tree = "64-B quantized" if kst.get("quantized") else "128-B exact"
+    head = None
+    if rank == 0:
+        head = {"metric": METRIC, "value": round(float(W * h_img) * args.steps * DEPTH / elapsed / 1e6, 2),
+                "unit": "Msamples/s", "n_gpus": n, "steps": args.steps,
+                "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+                "higher_is_better": True, "scaling": "strong" if (strong_only and n > 1) else "weak",
+                "vs_baseline": None,
+                "dtype": "f32",
+                "data": "synthetic seeds; " + ("Scene/cbox geometry recovered from the reference's cbox.mb"
+                                               if args.workload == "C2" else "see config.workload"),
+                "config": {"workload": wl["desc"],
+                           "width": W, "height": h_img, "max_depth": DEPTH,
+                           "parallelism": "row-stripe tiles x%d" % n, "mode": "exact",
+                           "schedule": "paired" if dsc.schedule == L.SCHED_PAIRED else "single",
+                           "shade_threshold": shade_th,
+                           "fetch_threshold": rnd.get_tuning()["fetch_threshold"] or 1,
+                           "block_entries": rnd.get_tuning()["block_entries"] or 8,
+                           "frames_per_block": fpb,
+                           "last_block_frames": rnd.get_tuning()["last_block_frames"],
+                           "tile_order": {0: "dearest first (costliest pixel)", 1: "image", 2: "dearest first (summed)"}[
+                               rnd.get_tuning()["tile_order"]],
+                           "search_tree_nodes": search_tree,
+                           "search_tree_top_levels_in_lds": kst.get("top_levels"),
+                           "stack": "16-entry LDS window + HBM spill" if kst.get("stack_window") else "whole in LDS",
+                           "resident_waves": kst.get("workgroups")},
+                "scene_build_gpu_s": None if build_s is None else round(build_s, 3)}
+    if not args.full:
+        # a plain run: the headline alone
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        dsc.close()
+        rnd.close()
+        if ws > 1:
+            torch.distributed.destroy_process_group()
+        return head
+    # --full: everything below is measured after the headline, in runs of its own
     # the same frames with the primary-hit cache off (every frame traces its
     # primary ray), timed after the headline: the memoization's share of it
     cache_off = None
@@ -463,8 +555,6 @@ def main():
     # k_render alone: the call's device time less the primary-hit pass before it
     primary_ms = kst.get("primary_ms", 0.0) if kst.get("primary_cache") == 2 else 0.0
     kernel_ms, launches = kst["kernel_ms"] - primary_ms, max(kst["launches"], 1)
-    fpb = kst["frames_per_block"]
-    search_tree = "64-B quantized" if kst.get("quantized") else "128-B exact"
 
     # replay the same frames with counters on (deterministic: same segments)
     # (the counting kernel runs the replay's warmup too, so the timed launch
@@ -530,8 +620,6 @@ def main():
                                    "the headline's fixed image; speedup_vs_1gpu = the same image and call rendered "
                                    "whole by rank 0 alone in this job (auto plan) / the striped time")
 
-    total_samples = float(W * h_img) * args.steps * DEPTH
-    value = total_samples / elapsed / 1e6
     out = None
     if rank == 0:
         avg_launch_s = kernel_ms / 1e3 / launches
@@ -622,30 +710,9 @@ def main():
         cpu = None
         if n == 1 and not args.no_cpu and args.workload == "C2":
             cpu = cpu_baseline(data, cam, h_img)
-        out = {"metric": METRIC, "value": round(value, 2), "unit": "Msamples/s", "n_gpus": n, "steps": args.steps,
-               "warmup": args.warmup, "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
-               "higher_is_better": True, "scaling": "strong" if (strong_only and n > 1) else "weak",
-               "vs_baseline": None,
-               "dtype": "f32",
-               "data": "synthetic seeds; " + ("Scene/cbox geometry recovered from the reference's cbox.mb"
-                                              if args.workload == "C2" else "see config.workload"),
-               "config": {"workload": wl["desc"],
-                          "width": W, "height": h_img, "max_depth": DEPTH,
-                          "parallelism": "row-stripe tiles x%d" % n, "mode": "exact",
-                          "schedule": "paired" if dsc.schedule == L.SCHED_PAIRED else "single",
-                          "shade_threshold": shade_th,
-                          "fetch_threshold": rnd.get_tuning()["fetch_threshold"] or 1,
-                          "block_entries": rnd.get_tuning()["block_entries"] or 8,
-                          "frames_per_block": fpb,
-                          "last_block_frames": rnd.get_tuning()["last_block_frames"],
-                          "tile_order": {0: "dearest first (costliest pixel)", 1: "image", 2: "dearest first (summed)"}[
-                              rnd.get_tuning()["tile_order"]],
-                          "search_tree_nodes": search_tree,
-                          "search_tree_top_levels_in_lds": kst.get("top_levels"),
-                          "stack": "16-entry LDS window + HBM spill" if kst.get("stack_window") else "whole in LDS",
-                          "resident_waves": kst.get("workgroups")},
+        out = dict(head)
+        out.update({
                "active_Msegments_per_s": round(segments * n / elapsed / 1e6, 2),
-               "scene_build_gpu_s": None if build_s is None else round(build_s, 3),
                "traced_Msegments_per_s": round(traced * n / elapsed / 1e6, 2),
                "primary_cache_off": cache_off,
                "image_reduce_ms": None if reduce_ms is None else round(reduce_ms, 3),
@@ -659,7 +726,7 @@ def main():
                "c4_strong_speedup_vs_1gpu": (strong["speedup_vs_1gpu"] if (strong_only and strong) else
                                              (None if c4 is None else c4["speedup_vs_1gpu"])),
                "c4_strong_scaling": c4,
-               "roofline": roof, "cpu_baseline": cpu}
+               "roofline": roof, "cpu_baseline": cpu})
         print(json.dumps(out), flush=True)
     dsc.close()
     rnd.close()

@@ -846,6 +846,39 @@ def test_bench_strong_record():
     assert bench.strong_record(8, 8, 1, 1.0, [1.0], None, "n")["speedup_vs_1gpu"] is None
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.dump_outputs (--dump-outputs): hist as float32, count and seeds
+    exact in float64; an image over the byte budget is dumped as a fixed,
+    seeded pixel sample (the same one every call) with its indices, within
+    the budget."""
+    import bench
+    import torch
+    from montecarlopathtracing_amd.render import ImageState
+    assert bench.dump_pixels(1024 * 1024) is None  # the headline image is dumped whole
+    assert 2048 * 2048 * bench.DUMP_BYTES_PER_PIXEL > bench.DUMP_BUDGET  # C5's is sampled
+    seeds = np.arange(70, dtype=np.uint32) * np.uint32(61681) + np.uint32(0xFFFFFF00)
+    st = ImageState(10, 7, seeds, "cpu")
+    st.hist += torch.arange(280, dtype=torch.float32).reshape(70, 4) / 7
+    st.count += torch.arange(70, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "all"), st)
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["count.npy", "hist.npy", "seeds.npy"]
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in ("hist", "count", "seeds")}
+    assert got["hist"].dtype == np.float32 and np.array_equal(got["hist"], st.hist.numpy())
+    assert got["count"].dtype == np.float64 and np.array_equal(got["count"], np.arange(70))
+    assert got["seeds"].dtype == np.float64 and np.array_equal(got["seeds"].astype(np.uint32), seeds)
+    budget = 20 * (bench.DUMP_BYTES_PER_PIXEL + 8) + 5
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), st, budget=budget)
+    s1, s2 = ({k: np.load(str(tmp_path / d / (k + ".npy"))) for k in ("hist", "count", "seeds", "pixels")}
+              for d in ("s1", "s2"))
+    px = s1["pixels"].astype(np.int64)
+    assert len(px) == 20 and len(set(px)) == 20 and (np.diff(px) > 0).all() and 0 <= px[0] and px[-1] < 70
+    assert sum(v.nbytes for v in s1.values()) <= budget
+    assert np.array_equal(s1["hist"], st.hist.numpy()[px]) and np.array_equal(s1["count"], px)
+    assert np.array_equal(s1["seeds"].astype(np.uint32), seeds[px])
+    assert all(np.array_equal(s1[k], s2[k]) and s1[k].dtype in (np.float32, np.float64) for k in s1)
+
+
 def test_variant_names_map_to_macros(tmp_path):
     """`make variants` (the A/B builds tools/ab.py and tools/sweep.py time):
     each letter of a variant name sets its macro, the rest keep the shipped

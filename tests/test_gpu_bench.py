@@ -9,6 +9,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +33,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, MCPT_BENCH_SHARED_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
-                        "--steps", "4", "--warmup", "1", "--no-cpu"], cwd=ROOT, env=env, capture_output=True,
+                        "--steps", "4", "--warmup", "1", "--full", "--no-cpu"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _lines(r.stdout)
@@ -66,7 +67,7 @@ def test_bench_c4_strong_two_ranks_rehearsal():
     env = dict(os.environ, MCPT_BENCH_SHARED_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2",
-                        "--workload", "C4", "--steps", "2", "--warmup", "1", "--no-cpu"], cwd=ROOT, env=env,
+                        "--workload", "C4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _lines(r.stdout)[0]
@@ -79,10 +80,11 @@ def test_bench_c4_strong_two_ranks_rehearsal():
 
 
 def test_bench_default_line():
-    """The driver's own command at N = 1: the contract keys, a roofline whose
-    fractions are fractions, and the CPU baseline with its core count."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2"], cwd=ROOT, capture_output=True,
-                       text=True, timeout=300)
+    """The driver's own command at N = 1 with --full: the contract keys, a
+    roofline whose fractions are fractions, and the CPU baseline with its core
+    count."""
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--full"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _lines(r.stdout)[-1]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -102,3 +104,46 @@ def test_bench_default_line():
     assert j["primary_cache_off"]["value"] > 0
     cpu = j["cpu_baseline"]
     assert cpu["cores"] >= 1 and cpu["threads"] == cpu["cores"] and cpu["cpu_model"] and cpu["value"] > 0
+
+
+# what only --full measures: absent from a plain run's line
+FULL_ONLY = ("roofline", "cpu_baseline", "primary_cache_off", "host_dump", "active_Msegments_per_s",
+             "traced_Msegments_per_s", "image_reduce_ms", "strong_scaling", "c4_strong_scaling")
+
+
+def _plain(tmp, steps):
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+                        "--dump-outputs", str(tmp)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = _lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    return lines[0], {k: np.load(os.path.join(str(tmp), k + ".npy")) for k in ("hist", "count", "seeds")}
+
+
+def test_bench_plain_line_and_dump(tmp_path):
+    """A plain run: the headline keys and the plan, nothing --full measures;
+    --steps sets the timed frames; --dump-outputs writes the timed call's
+    image state, the same arrays from run to run."""
+    j, a = _plain(tmp_path / "a", 3)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config"):
+        assert k in j, k
+    for k in FULL_ONLY:
+        assert k not in j, k
+    assert j["n_gpus"] == 1 and j["steps"] == 3 and j["warmup"] == 1 and j["value"] > 0 and j["ms_per_step"] > 0
+    assert j["higher_is_better"] is True and j["unit"] == "Msamples/s" and j["dtype"] == "f32"
+    # value and ms_per_step are one measurement: pixels x depth per step time
+    assert j["value"] == pytest.approx(1024 * 1024 * 8 / j["ms_per_step"] / 1e3, rel=1e-3)
+    n = 1024 * 1024
+    assert sorted(os.listdir(str(tmp_path / "a"))) == ["count.npy", "hist.npy", "seeds.npy"]
+    assert a["hist"].shape == (n, 4) and a["hist"].dtype == np.float32
+    assert a["count"].shape == (n,) and a["count"].dtype == np.float64
+    assert a["seeds"].shape == (n,) and a["seeds"].dtype == np.float64
+    assert np.isfinite(a["hist"]).all() and float(a["hist"][:, :3].max()) > 0
+    # warmup + steps frames went through the state (a sample that returned
+    # black is not counted: history.cl)
+    assert a["count"].min() >= 0 and a["count"].max() == 1 + 3
+    assert sum(v.nbytes for v in a.values()) <= 64 * 1000 * 1000
+    _, b = _plain(tmp_path / "b", 3)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k

@@ -64,7 +64,8 @@ def sh(cmd, log, limit):
 def run(tag, args):
     out = os.path.join(ROOT, "gpurun_out", "prof_" + tag)
     os.makedirs(out, exist_ok=True)
-    bench = [sys.executable, os.path.join(ROOT, "bench.py")] + args
+    # --full: the line's roofline and the counting replay after the timed call
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + args
     print("bench:", " ".join(args), flush=True)
     with open(os.path.join(out, "bench.json"), "w") as fh:
         r = subprocess.run(["timeout", "-k", "10", "400"] + bench, stdout=fh, stderr=subprocess.PIPE, text=True)
