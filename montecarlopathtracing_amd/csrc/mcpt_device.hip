@@ -33,6 +33,7 @@
 #include "../../include/mcpt_hip.h"
 #include "mcpt_refmath.h"
 #include "mcpt_bvh4.h"
+#include "mcpt_plan.h"  // the launch plan and its constants (kHandoffWords, kHandoffMaxBytes, ...)
 #include "mcpt_upload.h"
 
 using namespace mcpt;
@@ -163,9 +164,6 @@ struct mcpt_scene {
 
 constexpr int kQueues = 8;         // k_render work queues (at most): one per XCD (MI355X has 8)
 constexpr int kQueueStride = 32;   // u32 words between queue heads: one 128-B line each
-constexpr int kDefaultBlockEntries = 8;  // mcpt_tuning.block_entries = 0 (launch plan, below)
-constexpr int kHandoffWords = 4;   // seed, mean.xyzw, count in four tagged 8-B granules (two 16-B stores)
-constexpr int kMaxBlocksPerLaunch = 255;  // the hand-off tag's 8 bits of block index
 constexpr int kStatSlots = 24;
 constexpr int64_t kQuantAutoBytes = 32ll << 20;  // 8 XCDs x 4 MiB of L2
 // primary-hit pass: k_primary (one ray per lane) for search trees up to this
@@ -240,7 +238,7 @@ struct mcpt_ctx {
   int64_t px_cap = 0;                     // their capacity in pixels (a larger image collects nothing)
   unsigned long long *d_stats = nullptr;  // segments, nodes, tris, bad, wave T/L/S phases
   uint32_t *d_queue = nullptr;            // k_render work-queue heads, kQueues per launch
-  int32_t queue_cap = 0;                  // launches the head array holds
+  int64_t queue_cap = 0;                  // launches the head array holds
   unsigned long long *d_handoff = nullptr;  // k_render per-pixel block hand-off granules
   int64_t handoff_cap = 0;                // pixels
   uint32_t launch_seq = 0;                // tags hand-off granules with the launch they belong to
@@ -289,6 +287,7 @@ struct mcpt_state {
     hipError_t e_ = (expr);                                                                 \
     if (e_ != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
+#define MCPT_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)  // propagate an MCPT_ERR_*
 
 // ----------------------------------------------------------------- traversal
 struct Trace {
@@ -766,7 +765,6 @@ __device__ inline f4 accumulate_one(f4 now, f4 &hist, int32_t &cnt, int max_atte
 // before the next memory instruction, a full memory round trip per 16 B.
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr uint32_t kHandoffMaxBytes = 0x7FFFFFFFu;  // images beyond it run without hand-offs (mcpt_render_frames)
 __device__ inline __amdgpu_buffer_rsrc_t handoff_rsrc(unsigned long long *base) {
   return __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)kHandoffMaxBytes, 0x00020000);
 }
@@ -1717,15 +1715,9 @@ int mcpt_ctx_destroy(mcpt_ctx *c) {
   (void)hipSetDevice(c->device);
   if (c->d_stats) (void)hipFree(c->d_stats);
   if (c->last_pending && c->ev1) (void)hipEventSynchronize(c->ev1);  // the last render may still use the buffers
-  if (c->d_queue) (void)hipFree(c->d_queue);
-  if (c->d_handoff) (void)hipFree(c->d_handoff);
-  if (c->d_spill) (void)hipFree(c->d_spill);
-  if (c->d_prim) (void)hipFree(c->d_prim);
-  if (c->d_prim_cost) (void)hipFree(c->d_prim_cost);
-  if (c->d_tile_order) (void)hipFree(c->d_tile_order);
-  if (c->d_tile_key) (void)hipFree(c->d_tile_key);
-  if (c->d_wave_log) (void)hipFree(c->d_wave_log);
-  if (c->d_entry_log) (void)hipFree(c->d_entry_log);
+  for (void *p : {(void *)c->d_queue, (void *)c->d_handoff, (void *)c->d_spill, (void *)c->d_prim, (void *)c->d_prim_cost,
+                  (void *)c->d_tile_order, (void *)c->d_tile_key, (void *)c->d_wave_log, (void *)c->d_entry_log})
+    if (p) (void)hipFree(p);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_prim) (void)hipEventDestroy(c->ev_prim);
@@ -2071,24 +2063,19 @@ int mcpt_state_destroy(mcpt_state *s) {
   if (!s) return MCPT_OK;
   (void)hipSetDevice(s->device);
   (void)hipDeviceSynchronize();  // work enqueued on the state may still be running
-  if (s->seeds) (void)hipFree(s->seeds);
-  if (s->hist) (void)hipFree(s->hist);
-  if (s->count) (void)hipFree(s->count);
+  for (void *p : {(void *)s->seeds, (void *)s->hist, (void *)s->count})
+    if (p) (void)hipFree(p);
   delete s;
   return MCPT_OK;
 }
 
-int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, const mcpt_bvh_node *nodes,
-                      int64_t n_nodes, const mcpt_material *mats, int32_t n_mats, mcpt_scene **out) {
-  if (!ctx || !tris || !nodes || !mats || !out || n_tris <= 0 || n_mats <= 0)
-    return mcpt::fail(MCPT_ERR_ARG, "scene_upload: bad argument");
-  if (n_nodes != 2 * n_tris - 1) return mcpt::fail(MCPT_ERR_ARG, "scene_upload: expected 2n-1 BVH nodes");
-  int32_t depth = 0;
-  int rc = mcpt_bvh_stack_depth(nodes, n_nodes, &depth);
-  if (rc) return rc;
-  if (depth > 64) return mcpt::fail(MCPT_ERR_LIMIT, "scene_upload: BVH deeper than the reference's 64-entry stack");
-  const int64_t n = n_tris;
-  // validate links and material ids before anything reaches the GPU
+// The host steps of mcpt_scene_upload, in call order.  First the tree's shape, links, material ids
+// and vertices, before anything reaches the GPU; *depth = the reference tree's DFS stack bound.
+static int validate_scene(const mcpt_triangle *tris, int64_t n, const mcpt_bvh_node *nodes, int64_t n_nodes,
+                          int32_t n_mats, int32_t *depth) {
+  if (n_nodes != 2 * n - 1) return mcpt::fail(MCPT_ERR_ARG, "scene_upload: expected 2n-1 BVH nodes");
+  MCPT_TRY(mcpt_bvh_stack_depth(nodes, n_nodes, depth));
+  if (*depth > 64) return mcpt::fail(MCPT_ERR_LIMIT, "scene_upload: BVH deeper than the reference's 64-entry stack");
   for (int64_t i = 0; i < n_nodes; ++i) {
     const mcpt_bvh_node &b = nodes[i];
     if (b.left < 0 || b.right < 0) return mcpt::fail(MCPT_ERR_ARG, "scene_upload: negative child index");
@@ -2107,14 +2094,19 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
         if (!std::isfinite(tris[i].v[k][j]))
           return mcpt::fail(MCPT_ERR_ARG, "scene_upload: non-finite vertex coordinate");
   }
-  // reference node index -> device index: internal nodes keep their index in
-  // a compacted array (the HLBVH puts them at [0, n-2]); leaves become ~tri.
+  return MCPT_OK;
+}
+
+// The 64-B nodes.  Reference node index -> device index: internal nodes keep
+// their index in a compacted array (the HLBVH puts them at [0, n-2]); leaves
+// become ~tri.  *n_int = the internal nodes; dn holds at least one record.
+static int build_nodes(const mcpt_bvh_node *nodes, int64_t n_nodes, std::vector<DevNode> &dn, int64_t *n_int) {
   std::vector<int32_t> remap(n_nodes, -1);
-  int64_t n_int = 0;
+  *n_int = 0;
   for (int64_t i = 0; i < n_nodes; ++i)
-    if (nodes[i].left != nodes[i].right) remap[i] = (int32_t)n_int++;
+    if (nodes[i].left != nodes[i].right) remap[i] = (int32_t)(*n_int)++;
   auto child = [&](int32_t c) -> int32_t { return nodes[c].left == nodes[c].right ? ~nodes[c].left : remap[c]; };
-  std::vector<DevNode> dn(std::max<int64_t>(n_int, 1));
+  dn.resize(std::max<int64_t>(*n_int, 1));
   std::memset(dn.data(), 0, dn.size() * sizeof(DevNode));
   for (int64_t i = 0; i < n_nodes; ++i) {
     if (remap[i] < 0) continue;
@@ -2126,60 +2118,65 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
     d.left = child(b.left);
     d.right = child(b.right);
   }
-  if (n_int > 0 && remap[0] != 0) return mcpt::fail(MCPT_ERR_ARG, "scene_upload: root must be node 0");
-  // 4-wide collapse (DevNode4): breadth-first over the binary internal nodes
-  // that start a 4-wide node (the root and every internal grandchild).
-  std::vector<DevNode4> dn4;
-  int32_t depth4 = 1;
-  if (n_int > 0) {
-    std::vector<int32_t> order(1, 0);  // binary ids of 4-wide nodes, index = DevNode4 id
-    std::vector<int32_t> need;         // stack entries needed below each 4-wide node
-    for (size_t k = 0; k < order.size(); ++k) {
-      const mcpt_bvh_node &b = nodes[order[k]];
-      DevNode4 q;
-      std::memset(&q, 0, sizeof(q));
-      int slot = 0;
-      auto put = [&](int32_t c) {
-        const mcpt_bvh_node &x = nodes[c];
-        float v[6] = {x.bbmin[0], x.bbmax[0], x.bbmin[1], x.bbmax[1], x.bbmin[2], x.bbmax[2]};
-        float *qf = reinterpret_cast<float *>(q.q);
-        std::memcpy(qf + 6 * slot, v, sizeof(v));
-        if (x.left == x.right) {
-          q.link[slot] = ~x.left;
-        } else {
-          q.link[slot] = (int32_t)order.size();
-          order.push_back(c);
-        }
-        ++slot;
-      };
-      for (int32_t c : {b.left, b.right}) {
-        const mcpt_bvh_node &x = nodes[c];
-        if (x.left == x.right) {
-          put(c);
-        } else {
-          put(x.left);
-          put(x.right);
-        }
-      }
-      for (; slot < 4; ++slot) q.link[slot] = kEmptySlot;
-      dn4.push_back(q);
-    }
-    // stack need: visiting slot i of a k-slot node leaves k-1-i entries pending
-    need.assign(dn4.size(), 0);
-    for (int64_t k = (int64_t)dn4.size() - 1; k >= 0; --k) {  // children have larger ids
-      int ns = 0;
-      while (ns < 4 && dn4[k].link[ns] != kEmptySlot) ++ns;
-      int best = ns - 1;
-      for (int i = 0; i < ns; ++i)
-        if (dn4[k].link[i] >= 0) best = std::max(best, ns - 1 - i + need[dn4[k].link[i]]);
-      need[k] = best;
-    }
-    depth4 = std::max(need[0], 1);
-  } else {
+  if (*n_int > 0 && remap[0] != 0) return mcpt::fail(MCPT_ERR_ARG, "scene_upload: root must be node 0");
+  return MCPT_OK;
+}
+
+// 4-wide collapse (DevNode4): breadth-first over the binary internal nodes
+// that start a 4-wide node (the root and every internal grandchild).  Returns
+// the stack entries a traversal of dn4 needs (at least 1).
+static int32_t collapse4(const mcpt_bvh_node *nodes, int64_t n_int, std::vector<DevNode4> &dn4) {
+  if (n_int <= 0) {
     dn4.resize(1);
     std::memset(dn4.data(), 0, sizeof(DevNode4));
+    return 1;
   }
-  // the EXACT search tree over the reference's own leaves (their boxes as stored)
+  std::vector<int32_t> order(1, 0);  // binary ids of 4-wide nodes, index = DevNode4 id
+  for (size_t k = 0; k < order.size(); ++k) {
+    const mcpt_bvh_node &b = nodes[order[k]];
+    DevNode4 q;
+    std::memset(&q, 0, sizeof(q));
+    int slot = 0;
+    auto put = [&](int32_t c) {
+      const mcpt_bvh_node &x = nodes[c];
+      float v[6] = {x.bbmin[0], x.bbmax[0], x.bbmin[1], x.bbmax[1], x.bbmin[2], x.bbmax[2]};
+      float *qf = reinterpret_cast<float *>(q.q);
+      std::memcpy(qf + 6 * slot, v, sizeof(v));
+      if (x.left == x.right) {
+        q.link[slot] = ~x.left;
+      } else {
+        q.link[slot] = (int32_t)order.size();
+        order.push_back(c);
+      }
+      ++slot;
+    };
+    for (int32_t c : {b.left, b.right}) {
+      const mcpt_bvh_node &x = nodes[c];
+      if (x.left == x.right) {
+        put(c);
+      } else {
+        put(x.left);
+        put(x.right);
+      }
+    }
+    for (; slot < 4; ++slot) q.link[slot] = kEmptySlot;
+    dn4.push_back(q);
+  }
+  // stack need: visiting slot i of a k-slot node leaves k-1-i entries pending
+  std::vector<int32_t> need(dn4.size(), 0);  // stack entries needed below each 4-wide node
+  for (int64_t k = (int64_t)dn4.size() - 1; k >= 0; --k) {  // children have larger ids
+    int ns = 0;
+    while (ns < 4 && dn4[k].link[ns] != kEmptySlot) ++ns;
+    int best = ns - 1;
+    for (int i = 0; i < ns; ++i)
+      if (dn4[k].link[i] >= 0) best = std::max(best, ns - 1 - i + need[dn4[k].link[i]]);
+    need[k] = best;
+  }
+  return std::max(need[0], 1);
+}
+
+// The reference's own leaves (their boxes as stored), the EXACT search tree's input.
+static std::vector<mcpt::LeafRef> leaf_list(const mcpt_bvh_node *nodes, int64_t n_nodes, int64_t n) {
   std::vector<mcpt::LeafRef> leaves;
   leaves.reserve((size_t)n);
   for (int64_t i = 0; i < n_nodes; ++i) {
@@ -2191,18 +2188,10 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
     L.tri = b.left;
     leaves.push_back(L);
   }
-  std::vector<mcpt::Node4Rec> near;
-  int32_t depth_near = 1;
-  if (n_int > 0) {
-    const unsigned hw = std::thread::hardware_concurrency();
-    if (mcpt::build_sah4(leaves, near, &depth_near, (int)std::min(16u, std::max(1u, hw))) != 0)
-      return mcpt::fail(MCPT_ERR_ARG, "scene_upload: no leaves");
-  } else {
-    near.resize(1);
-    std::memset(near.data(), 0, sizeof(mcpt::Node4Rec));
-  }
-  depth4 = std::max(depth4, depth_near);
-  if (depth4 > 192) return mcpt::fail(MCPT_ERR_LIMIT, "scene_upload: 4-wide stack too deep");
+  return leaves;
+}
+
+static std::vector<DevTri> pack_tris(const mcpt_triangle *tris, int64_t n) {
   std::vector<DevTri> dt(n);
   for (int64_t i = 0; i < n; ++i) {
     const mcpt_triangle &t = tris[i];
@@ -2216,14 +2205,18 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
     d.nac = (f4){c1, c2, c3, t.normal[2]};
     d.aux = (f4){t.normal[3], std::fma(b2, c3, -(c2 * b3)), std::fma(b1, c3, -(c1 * b3)), std::fma(b1, c2, -(c1 * b2))};
   }
-  // The quantized search tree: 64-B nodes whose decoded
-  // boxes strictly contain the exact ones, so every box test is a superset of
-  // the exact one, and the L phase re-tests the reference leaf's own box,
-  // rebuilt from the triangle's vertices -- valid when every reference leaf's
-  // box IS min/max of its vertices (hlbvh.cpp:97-100; a foreign tree may differ,
-  // and then keeps the 128-B path).
-  std::vector<DevNode4Q> nq;
-  std::vector<DevTriQ> tq;
+  return dt;
+}
+
+// The quantized search tree: 64-B nodes whose decoded
+// boxes strictly contain the exact ones, so every box test is a superset of
+// the exact one, and the L phase re-tests the reference leaf's own box,
+// rebuilt from the triangle's vertices -- valid when every reference leaf's
+// box IS min/max of its vertices (hlbvh.cpp:97-100; a foreign tree may differ,
+// and then keeps the 128-B path).  Returns whether nq and tq were built.
+static bool quantize_tree(const mcpt_triangle *tris, int64_t n, const mcpt_bvh_node *nodes, int64_t n_nodes,
+                          int64_t n_int, const std::vector<mcpt::Node4Rec> &near, const std::vector<DevTri> &dt,
+                          std::vector<DevNode4Q> &nq, std::vector<DevTriQ> &tq) {
   bool quant = n_int > 0;
   for (int64_t i = 0; quant && i < n_nodes; ++i) {
     const mcpt_bvh_node &b = nodes[i];
@@ -2240,76 +2233,92 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
     for (size_t k = 0; quant && k < near.size(); ++k)
       quant = mcpt::quantize_node4(near[k], *reinterpret_cast<mcpt::Node4Q *>(&nq[k])) == 0;
   }
-  if (quant) {
-    tq.resize(n);
-    for (int64_t i = 0; i < n; ++i) {
-      const mcpt_triangle &t = tris[i];
-      tq[i].v0 = (f4){t.v[0][0], t.v[0][1], t.v[0][2], dt[i].aux.y};
-      tq[i].v1 = (f4){t.v[1][0], t.v[1][1], t.v[1][2], dt[i].aux.z};
-      tq[i].v2 = (f4){t.v[2][0], t.v[2][1], t.v[2][2], dt[i].aux.w};
-      tq[i].nrm = (f4){t.normal[0], t.normal[1], t.normal[2], t.normal[3]};
-    }
-  } else {
+  if (!quant) {
     nq.clear();
+    return false;
   }
-  // pruning margin: 2^-10 of the scene diagonal (DESIGN.md §3.2)
-  const mcpt_bvh_node &root = nodes[0];
-  float dx = root.bbmax[0] - root.bbmin[0], dy = root.bbmax[1] - root.bbmin[1], dz = root.bbmax[2] - root.bbmin[2];
-  float diag = std::sqrt(dx * dx + dy * dy + dz * dz);
+  tq.resize(n);
+  for (int64_t i = 0; i < n; ++i) {
+    const mcpt_triangle &t = tris[i];
+    tq[i].v0 = (f4){t.v[0][0], t.v[0][1], t.v[0][2], dt[i].aux.y};
+    tq[i].v1 = (f4){t.v[1][0], t.v[1][1], t.v[1][2], dt[i].aux.z};
+    tq[i].v2 = (f4){t.v[2][0], t.v[2][1], t.v[2][2], dt[i].aux.w};
+    tq[i].nrm = (f4){t.normal[0], t.normal[1], t.normal[2], t.normal[3]};
+  }
+  return true;
+}
 
-  HIP_OK(hipSetDevice(ctx->device));
-  static std::atomic<uint64_t> scene_uids{0};
-  mcpt_scene *s = new mcpt_scene();
-  s->uid = ++scene_uids;
-  s->device = ctx->device;
-  if (hipMalloc(&s->near4, near.size() * sizeof(DevNode4)) != hipSuccess ||
-      hipMalloc(&s->nodes4, dn4.size() * sizeof(DevNode4)) != hipSuccess ||
-      hipMalloc(&s->nodes, dn.size() * sizeof(DevNode)) != hipSuccess ||
-      hipMalloc(&s->tris, dt.size() * sizeof(DevTri)) != hipSuccess ||
-      hipMalloc(&s->mats, n_mats * sizeof(mcpt_material)) != hipSuccess) {
-    mcpt_scene_destroy(s);
-    return mcpt::fail(MCPT_ERR_HIP, "scene_upload: hipMalloc failed");
-  }
-  if (hipMemcpy(s->near4, near.data(), near.size() * sizeof(DevNode4), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s->nodes4, dn4.data(), dn4.size() * sizeof(DevNode4), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s->nodes, dn.data(), dn.size() * sizeof(DevNode), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s->tris, dt.data(), dt.size() * sizeof(DevTri), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(s->mats, mats, n_mats * sizeof(mcpt_material), hipMemcpyHostToDevice) != hipSuccess) {
-    mcpt_scene_destroy(s);
-    return mcpt::fail(MCPT_ERR_HIP, "scene_upload: hipMemcpy failed");
-  }
-  if (quant && (hipMalloc(&s->near4q, nq.size() * sizeof(DevNode4Q)) != hipSuccess ||
-                hipMalloc(&s->triq, tq.size() * sizeof(DevTriQ)) != hipSuccess ||
-                hipMemcpy(s->near4q, nq.data(), nq.size() * sizeof(DevNode4Q), hipMemcpyHostToDevice) != hipSuccess ||
-                hipMemcpy(s->triq, tq.data(), tq.size() * sizeof(DevTriQ), hipMemcpyHostToDevice) != hipSuccess)) {
-    mcpt_scene_destroy(s);
-    return mcpt::fail(MCPT_ERR_HIP, "scene_upload: quantized tree upload failed");
-  }
-  s->n_tris = n;
-  s->near4_bytes = (int64_t)(near.size() * sizeof(DevNode4));
-  s->n_internal = n_int;
-  s->n_mats = n_mats;
+// What both upload paths record once the device arrays are in *s: the counts, the
+// stack depths and the whole SceneView.  n_int: the tree's internal nodes (the
+// nodes array holds at least one record); root: a host copy of node 0.
+static void finish_scene(mcpt_scene *s, uint64_t uid, int64_t n_tris, int64_t n_near4, int64_t n_nodes4, int64_t n_int,
+                         const mcpt_material *mats, int32_t n_mats, int32_t depth, int32_t depth4,
+                         const mcpt_bvh_node &root) {
+  s->uid = uid, s->n_tris = n_tris, s->n_internal = n_int, s->n_mats = n_mats;
+  s->near4_bytes = n_near4 * (int64_t)sizeof(DevNode4);
   s->has_glossy = false;
   for (int32_t k = 0; k < n_mats; ++k) s->has_glossy |= mats[k].type == MCPT_GLOSSY;
-  s->stack_depth = std::max(depth, 1);
-  s->stack_depth4 = depth4;
+  s->stack_depth = std::max(depth, 1), s->stack_depth4 = depth4;
   SceneView &v = s->view;
-  v.n_near4 = (int32_t)near.size();
-  v.n_nodes4 = (int32_t)dn4.size();
-  v.n_int = (int32_t)dn.size();
-  v.n_tris = n;
-  v.nodes = s->nodes;
-  v.nodes4 = s->nodes4;
-  v.near4 = s->near4;
-  v.tris = s->tris;
-  v.near4q = s->near4q;
-  v.triq = s->triq;
-  v.mats = s->mats;
+  v.n_near4 = (int32_t)n_near4, v.n_nodes4 = (int32_t)n_nodes4, v.n_int = (int32_t)std::max<int64_t>(n_int, 1);
+  v.n_tris = n_tris, v.n_mats = n_mats;
+  v.nodes = s->nodes, v.nodes4 = s->nodes4, v.near4 = s->near4, v.near4q = s->near4q;
+  v.tris = s->tris, v.triq = s->triq, v.mats = s->mats;
   v.root_min = (f4){root.bbmin[0], root.bbmin[1], root.bbmin[2], root.bbmin[3]};
   v.root_max = (f4){root.bbmax[0], root.bbmax[1], root.bbmax[2], root.bbmax[3]};
   v.root_leaf = root.left == root.right ? root.left : -1;
-  v.n_mats = n_mats;
+  // pruning margin: 2^-10 of the scene diagonal (DESIGN.md §3.2)
+  float dx = root.bbmax[0] - root.bbmin[0], dy = root.bbmax[1] - root.bbmin[1], dz = root.bbmax[2] - root.bbmin[2];
+  float diag = std::sqrt(dx * dx + dy * dy + dz * dz);
   v.prune_margin = std::isfinite(diag) ? std::ldexp(diag, -10) : __builtin_inff();
+}
+
+int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, const mcpt_bvh_node *nodes,
+                      int64_t n_nodes, const mcpt_material *mats, int32_t n_mats, mcpt_scene **out) {
+  if (!ctx || !tris || !nodes || !mats || !out || n_tris <= 0 || n_mats <= 0)
+    return mcpt::fail(MCPT_ERR_ARG, "scene_upload: bad argument");
+  const int64_t n = n_tris;
+  int32_t depth = 0, depth_near = 1;
+  MCPT_TRY(validate_scene(tris, n, nodes, n_nodes, n_mats, &depth));
+  std::vector<DevNode> dn;
+  int64_t n_int = 0;
+  MCPT_TRY(build_nodes(nodes, n_nodes, dn, &n_int));
+  std::vector<DevNode4> dn4;
+  int32_t depth4 = collapse4(nodes, n_int, dn4);
+  // the EXACT search tree over the reference's own leaves
+  std::vector<mcpt::Node4Rec> near;
+  if (n_int > 0) {
+    const unsigned hw = std::thread::hardware_concurrency();
+    if (mcpt::build_sah4(leaf_list(nodes, n_nodes, n), near, &depth_near, (int)std::min(16u, std::max(1u, hw))) != 0)
+      return mcpt::fail(MCPT_ERR_ARG, "scene_upload: no leaves");
+  } else {
+    near.resize(1);
+    std::memset(near.data(), 0, sizeof(mcpt::Node4Rec));
+  }
+  depth4 = std::max(depth4, depth_near);
+  if (depth4 > 192) return mcpt::fail(MCPT_ERR_LIMIT, "scene_upload: 4-wide stack too deep");
+  const std::vector<DevTri> dt = pack_tris(tris, n);
+  std::vector<DevNode4Q> nq;
+  std::vector<DevTriQ> tq;
+  const bool quant = quantize_tree(tris, n, nodes, n_nodes, n_int, near, dt, nq, tq);
+
+  HIP_OK(hipSetDevice(ctx->device));
+  mcpt_scene *s = new mcpt_scene();
+  s->device = ctx->device;
+  auto put = [](auto **dst, const void *src, size_t bytes) {  // one device array, allocated and filled
+    return hipMalloc(dst, bytes) == hipSuccess && hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  };
+  if (!put(&s->near4, near.data(), near.size() * sizeof(DevNode4)) ||
+      !put(&s->nodes4, dn4.data(), dn4.size() * sizeof(DevNode4)) ||
+      !put(&s->nodes, dn.data(), dn.size() * sizeof(DevNode)) || !put(&s->tris, dt.data(), dt.size() * sizeof(DevTri)) ||
+      !put(&s->mats, mats, n_mats * sizeof(mcpt_material)) ||
+      (quant && (!put(&s->near4q, nq.data(), nq.size() * sizeof(DevNode4Q)) ||
+                 !put(&s->triq, tq.data(), tq.size() * sizeof(DevTriQ))))) {
+    mcpt_scene_destroy(s);
+    return mcpt::fail(MCPT_ERR_HIP, "scene_upload: device allocation or copy failed");
+  }
+  static std::atomic<uint64_t> scene_uids{0};
+  finish_scene(s, ++scene_uids, n, (int64_t)near.size(), (int64_t)dn4.size(), n_int, mats, n_mats, depth, depth4, nodes[0]);
   *out = s;
   return MCPT_OK;
 }
@@ -2326,57 +2335,22 @@ int mcpt_scene_upload_device(mcpt_ctx *ctx, const mcpt_triangle *tris_dev, int64
   HIP_OK(hipSetDevice(ctx->device));
   mcpt::DeviceScene D;
   int rc = mcpt::build_scene_device(tris_dev, n_tris, nodes_dev, n_mats, (hipStream_t)stream, &D);
-  auto free_d = [&]() {
-    for (void *p : {D.near4, D.near4q, D.nodes4, D.nodes, D.tris, D.triq})
-      if (p) (void)hipFree(p);
-  };
+  mcpt_scene *s = new mcpt_scene();  // owns D's arrays from here, on failure too
+  s->device = ctx->device;
+  s->near4 = (DevNode4 *)D.near4, s->near4q = (DevNode4Q *)D.near4q;
+  s->nodes4 = (DevNode4 *)D.nodes4, s->nodes = (DevNode *)D.nodes;
+  s->tris = (DevTri *)D.tris, s->triq = (DevTriQ *)D.triq;
   if (rc != MCPT_OK) {
-    free_d();
+    mcpt_scene_destroy(s);
     return rc;
   }
-  static std::atomic<uint64_t> scene_uids_d{1ull << 62};  // distinct from mcpt_scene_upload's
-  mcpt_scene *s = new mcpt_scene();
-  s->uid = ++scene_uids_d;
-  s->device = ctx->device;
-  s->near4 = (DevNode4 *)D.near4;
-  s->near4q = (DevNode4Q *)D.near4q;
-  s->nodes4 = (DevNode4 *)D.nodes4;
-  s->nodes = (DevNode *)D.nodes;
-  s->tris = (DevTri *)D.tris;
-  s->triq = (DevTriQ *)D.triq;
   if (hipMalloc(&s->mats, n_mats * sizeof(mcpt_material)) != hipSuccess ||
       hipMemcpy(s->mats, mats, n_mats * sizeof(mcpt_material), hipMemcpyHostToDevice) != hipSuccess) {
     mcpt_scene_destroy(s);
     return mcpt::fail(MCPT_ERR_HIP, "scene_upload_device: material upload failed");
   }
-  const mcpt_bvh_node &root = D.root;
-  s->n_tris = n_tris;
-  s->near4_bytes = D.n_near4 * (int64_t)sizeof(DevNode4);
-  s->n_internal = D.n_int;
-  s->n_mats = n_mats;
-  s->has_glossy = false;
-  for (int32_t k = 0; k < n_mats; ++k) s->has_glossy |= mats[k].type == MCPT_GLOSSY;
-  s->stack_depth = std::max(D.stack_depth, 1);
-  s->stack_depth4 = D.depth4;
-  float dx = root.bbmax[0] - root.bbmin[0], dy = root.bbmax[1] - root.bbmin[1], dz = root.bbmax[2] - root.bbmin[2];
-  float diag = std::sqrt(dx * dx + dy * dy + dz * dz);
-  SceneView &v = s->view;
-  v.n_near4 = (int32_t)D.n_near4;
-  v.n_nodes4 = (int32_t)D.n_nodes4;
-  v.n_int = (int32_t)std::max<int64_t>(D.n_int, 1);
-  v.n_tris = n_tris;
-  v.nodes = s->nodes;
-  v.nodes4 = s->nodes4;
-  v.near4 = s->near4;
-  v.tris = s->tris;
-  v.near4q = s->near4q;
-  v.triq = s->triq;
-  v.mats = s->mats;
-  v.root_min = (f4){root.bbmin[0], root.bbmin[1], root.bbmin[2], root.bbmin[3]};
-  v.root_max = (f4){root.bbmax[0], root.bbmax[1], root.bbmax[2], root.bbmax[3]};
-  v.root_leaf = root.left == root.right ? root.left : -1;
-  v.n_mats = n_mats;
-  v.prune_margin = std::isfinite(diag) ? std::ldexp(diag, -10) : __builtin_inff();
+  static std::atomic<uint64_t> scene_uids_d{1ull << 62};  // distinct from mcpt_scene_upload's
+  finish_scene(s, ++scene_uids_d, n_tris, D.n_near4, D.n_nodes4, D.n_int, mats, n_mats, D.stack_depth, D.depth4, D.root);
   *out = s;
   return MCPT_OK;
 }
@@ -2415,13 +2389,9 @@ int mcpt_scene_read(const mcpt_scene *s, int32_t which, void *host, int64_t cap,
 int mcpt_scene_destroy(mcpt_scene *s) {
   if (!s) return MCPT_OK;
   (void)hipSetDevice(s->device);
-  if (s->nodes) (void)hipFree(s->nodes);
-  if (s->nodes4) (void)hipFree(s->nodes4);
-  if (s->near4) (void)hipFree(s->near4);
-  if (s->tris) (void)hipFree(s->tris);
-  if (s->near4q) (void)hipFree(s->near4q);
-  if (s->triq) (void)hipFree(s->triq);
-  if (s->mats) (void)hipFree(s->mats);
+  for (void *p : {(void *)s->nodes, (void *)s->nodes4, (void *)s->near4, (void *)s->tris, (void *)s->near4q,
+                  (void *)s->triq, (void *)s->mats})
+    if (p) (void)hipFree(p);
   delete s;
   return MCPT_OK;
 }
@@ -2454,44 +2424,39 @@ static int check_render(const mcpt_render_params *p) {
   return MCPT_OK;
 }
 
-int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_render_params *p,
-                       uint32_t *seeds, float *hist, int32_t *count, void *stream) {
-  if (!ctx || !scene || !cam || !p || !seeds || !hist || !count) return mcpt::fail(MCPT_ERR_ARG, "render: null argument");
-  int rc = check_render(p);
-  if (rc) return rc;
-  HIP_OK(hipSetDevice(ctx->device));
-  hipStream_t st = (hipStream_t)stream;
-  RenderArgs A;
-  A.cam = *cam;
-  A.S = scene->view;
-  A.seeds = seeds;
-  A.hist = (f4 *)hist;
-  A.count = count;
-  A.stats = ctx->d_stats;
-  A.W = p->width;
-  A.H = p->height;
-  A.stripe_rows = p->stripe_rows;
-  A.stripe_index = p->stripe_index;
-  A.stripe_count = p->stripe_count;
-  // rows owned by this stripe residue
-  int32_t full = p->height / (p->stripe_rows * p->stripe_count);
-  int32_t rem = p->height - full * p->stripe_rows * p->stripe_count;
-  int32_t extra = std::min(std::max(rem - p->stripe_index * p->stripe_rows, 0), p->stripe_rows);
-  A.local_rows = full * p->stripe_rows + extra;
-  A.tiles_x = (p->width + 7) / 8;
-  A.max_depth = p->max_depth;
-  A.max_attempt = p->max_attempt;
-  A.stack_depth = scene->stack_depth;
-  // tuned (tools/sweep.py, tools/ab.py): leaf phase at >= 4 lanes
-  // (single-leaf schedule) or >= 16 (paired), shade at >= 32
+// Ensures that a context buffer *a (and *b, a second one of the same capacity)
+// holds at least `need` elements of a_bytes (b_bytes); `cap` counts elements.
+// Nulls the pointers and zeroes the cap before it frees and allocates, so a
+// failed call leaves nothing for mcpt_ctx_destroy to free twice.
+static int grow_dev(int64_t &cap, int64_t need, void **a, size_t a_bytes, void **b = nullptr, size_t b_bytes = 0) {
+  if (need <= cap) return MCPT_OK;
+  void *old_a = *a, *old_b = b ? *b : nullptr;
+  *a = nullptr;
+  if (b) *b = nullptr;
+  cap = 0;
+  if (old_a) HIP_OK(hipFree(old_a));
+  if (old_b) HIP_OK(hipFree(old_b));
+  HIP_OK(hipMalloc(a, (size_t)need * a_bytes));
+  if (b) HIP_OK(hipMalloc(b, (size_t)need * b_bytes));
+  cap = need;
+  return MCPT_OK;
+}
+
+// The k_render instantiation of a render call and what it runs with.
+struct KernelChoice {
+  const void *fn, *prim_fn;  // prim_fn: its PRIM form (the primary-hit pass of large trees), no stats
+  size_t lds;                // dynamic LDS bytes of either
+  bool win;                  // the windowed stack
+  int per_cu;                // resident workgroups of fn per CU
+  int kind;                  // 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized
+  int depth_entries;         // the whole stack's entries per lane
+};
+
+// Picks the kernel and its stack window; fills A's lds_mats, top_levels, stack_depth and spill_stride.
+static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_render_params *p, RenderArgs &A,
+                         KernelChoice *K) {
   const mcpt_tuning &T = ctx->tune;
   const bool pair = p->schedule == MCPT_SCHED_PAIRED;
-  A.th_leaf = T.leaf_threshold > 0 ? T.leaf_threshold : (pair ? 16 : 4);
-  A.th_shade = T.shade_threshold > 0 ? T.shade_threshold : 32;
-  A.chunk = T.queue_chunk > 0 ? T.queue_chunk : 4;  // queue entries per atomic (at least)
-  A.th_fetch = T.fetch_threshold > 0 ? T.fetch_threshold : 1;
-  A.n_queues = T.queues > 0 ? (uint32_t)std::min(T.queues, kQueues) : (uint32_t)kQueues;
-  const int64_t tiles = (int64_t)A.tiles_x * ((A.local_rows + 7) / 8);
   const int depth_entries = p->mode == MCPT_MODE_NOPRUNE ? scene->stack_depth : scene->stack_depth4;
   A.lds_mats = scene->n_mats <= 256 ? 1 : 0;
   const size_t lds_mats = A.lds_mats ? scene->n_mats * sizeof(mcpt_material) : 0;
@@ -2540,354 +2505,239 @@ int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera
                              lds_mats + 15) & ~(size_t)15) + pad;
   const size_t lds_win = (((size_t)kWgWaves * kStackWindow * 64 * sizeof(int32_t) + sizeof(LdsUniforms) + lds_top +
                            lds_mats + 15) & ~(size_t)15) + pad;
-  bool win = false;
-  int per_cu = 0;
-  if (T.stack_window == 1) {  // forced (tests, experiments): the window even when the whole stack fits in it
-    win = true;
-    rc = occupancy(ctx, kfns[kind][ctx->stats_on][1][pair][glossy], lds_win, &per_cu);
-    if (rc) return rc;
-  } else if (depth_entries > kStackWindow && T.stack_window != 2) {
-    int per_cu_plain = 0, per_cu_win = 0;
-    rc = occupancy(ctx, kfns[kind][ctx->stats_on][0][pair][glossy], lds_plain, &per_cu_plain);
-    if (rc) return rc;
-    rc = occupancy(ctx, kfns[kind][ctx->stats_on][1][pair][glossy], lds_win, &per_cu_win);
-    if (rc) return rc;
-    win = per_cu_win > per_cu_plain;
-    per_cu = win ? per_cu_win : per_cu_plain;
-  } else {
-    rc = occupancy(ctx, kfns[kind][ctx->stats_on][0][pair][glossy], lds_plain, &per_cu);
-    if (rc) return rc;
-  }
-  const size_t lds = win ? lds_win : lds_plain;
-  const void *kfn = kfns[kind][ctx->stats_on][win][pair][glossy];
+  const void *const(*fns)[2][2] = kfns[kind][ctx->stats_on];  // [window][pair][glossy]
+  // stack_window 1 forces the window (tests, experiments) even when the whole stack fits in it, 2 forbids it
+  const bool forced = T.stack_window == 1;
+  int per_cu_plain = 0, per_cu_win = 0;
+  if (!forced) MCPT_TRY(occupancy(ctx, fns[0][pair][glossy], lds_plain, &per_cu_plain));
+  if (forced || (depth_entries > kStackWindow && T.stack_window != 2))
+    MCPT_TRY(occupancy(ctx, fns[1][pair][glossy], lds_win, &per_cu_win));
+  const bool win = forced || per_cu_win > per_cu_plain;
+  const int per_cu = win ? per_cu_win : per_cu_plain;
+  *K = {fns[win][pair][glossy], kpfns[kind][win][pair], win ? lds_win : lds_plain, win, per_cu, kind, depth_entries};
   A.stack_depth = win ? kStackWindow : depth_entries;  // the uniforms and material table follow the stack in LDS
   A.spill_stride = win ? std::max(0, depth_entries - kStackWindow) : 0;
-  // grid_wg workgroups of kWgWaves waves: `grid` waves (a tile per wave at most)
-  const int64_t grid_wg = std::max<int64_t>(
-      1, std::min<int64_t>((tiles + kWgWaves - 1) / kWgWaves, (int64_t)std::max(per_cu, 1) * ctx->n_cu));
-  const int64_t grid = grid_wg * kWgWaves;
-  const int64_t spill_need = win ? grid * 64 * (int64_t)A.spill_stride : 0;
-  if (win && spill_need > ctx->spill_cap) {
-    if (ctx->d_spill) HIP_OK(hipFree(ctx->d_spill));
-    ctx->d_spill = nullptr;
-    ctx->spill_cap = 0;
-    HIP_OK(hipMalloc(&ctx->d_spill, (size_t)spill_need * sizeof(int32_t)));
-    ctx->spill_cap = spill_need;
-  }
-  // frames_per_launch = frames per BLOCK: a lane runs one pixel for one block
-  // of frames, then hands the pixel's state to whichever lane takes its next
-  // block.  One launch runs many blocks of every pixel, block-major, so lanes
-  // stay busy until the last block (no per-block drain of the GPU).
-  // frames_per_launch <= 0: auto.  Blocks let the launch's tail shrink: the
-  // fewest blocks (at least 2) that give every resident lane `block_entries`
-  // queue entries (so the tail, where lanes run dry, is about
-  // 1/block_entries of the launch), frames split evenly over them, at most
-  // max_block_frames each.  Each block boundary costs a hand-off per pixel;
-  // with the packed hand-off, 8 entries and 2-3 blocks per call measured best
-  // (20-frame calls: C2 -2 %, C3 -11 %, C4 -1 %, C5 even against 32 entries;
-  // one block loses 2-7 % to the tail; profiles/r03_blocks.txt).
-  // That needs several entries per lane in each block (>= 4): a pixel's next
-  // block is then claimed long after its previous one started.  With fewer
-  // (small images, strong-scaled ranks: about one pixel per lane) every block
-  // boundary becomes a wait for the slowest pixel of the previous block, so
-  // blocks there keep at least 4 frames (measured on C2 and C4 shares of 2,
-  // 4 and 8 ranks, tools/sweep.py --stripes).
-  const uint32_t n_items = (uint32_t)A.tiles_x * (uint32_t)((A.local_rows + 7) / 8) * 64u;
-  const int cap = T.max_block_frames > 0 ? T.max_block_frames : 32;  // frames per block at most (auto plans)
-  int fpl = p->frames_per_launch;
-  bool tail_ok = false;  // auto plan with several entries per lane: a short last block may apply
-  double slots_per_px = 0;  // pixels per resident lane (auto plans)
-  const double px_per_lane =
-      (double)n_items / ((double)std::max(per_cu, 1) * ctx->n_cu * 64 * kWgWaves);  // vs resident lanes
-  if (fpl <= 0) {
-    const int frames = std::max(p->frames, 1);
-    const double per_block = (double)n_items / (double)(grid * 64);  // entries per lane per block
-    const int want = T.block_entries > 0 ? T.block_entries : kDefaultBlockEntries;
-    int nb = std::max(2, (int)std::ceil(want / std::max(per_block, 1e-9)));
-    nb = std::max(1, std::min(nb, frames));
-    fpl = (frames + nb - 1) / nb;
-    if (per_block < 4.0) fpl = std::max(fpl, 4);
-    // at most a few pixels per lane (strong-scaled ranks): little left to
-    // balance but the pixels' own chains, so one block per pixel below 0.75
-    // pixels per lane and two up to 2.5 (C2 shares of 4 and 8 ranks, C4 of 8:
-    // 1-12 % faster than 4-frame blocks; the C5 8-rank share, 2 pixels per
-    // lane: 4 % faster than 5-frame blocks; tools/sweep.py --stripes --fpl)
-    const double per_slot = px_per_lane;
-    slots_per_px = per_slot;
-    if (per_slot < 0.75)
-      fpl = frames;
-    else if (per_slot <= 2.5)
-      fpl = std::max(fpl, (frames + 1) / 2);
-    else
-      tail_ok = true;
-    fpl = std::max(1, std::min({fpl, cap, frames}));
-  }
-  // the hand-off area is addressed with 32-bit byte offsets below 2^31
-  // (handoff_rsrc): a larger image runs ONE block per launch, at most `cap`
-  // frames (no hand-off; launches chain through the state arrays, so every
-  // launch stays bounded: ~67 M+ pixels x 32 frames)
-  const bool no_handoff = (int64_t)p->width * p->height * kHandoffWords * 8 > (int64_t)kHandoffMaxBytes;
-  if (no_handoff) fpl = std::max(1, std::min(p->frames_per_launch > 0 ? p->frames_per_launch : std::max(p->frames, 1), cap));
-  // blocks per launch: the hand-off tag holds 8 bits of block index, and
-  // one launch covers at most ~4096 frames
-  const int64_t max_blocks = no_handoff ? 1 : std::max<int64_t>(
-      1, std::min<int64_t>({(int64_t)INT32_MAX / std::max<uint32_t>(n_items, 1), 4096 / fpl + 1,
-                            (int64_t)kMaxBlocksPerLaunch}));
-  const int64_t n_blocks_all = (p->frames + fpl - 1) / fpl;
-  const int n_launch = (int)((n_blocks_all + max_blocks - 1) / max_blocks);
-  // a short last block (last_block_frames, auto plans of one launch with
-  // several entries per lane): the first nb-1 blocks share frames - L evenly
-  // and the last takes the remainder (<= L).  Entries are block-major, so the
-  // last block's entries are the launch's tail; shorter ones leave lanes idle
-  // for less time at its end.  Same blocks, same hand-offs, same bits.
-  // Auto: ceil(frames / 8) frames once a lane has at least 6 pixels (20-frame
-  // C3 -2 %, 16-frame C4 -2 %, 8-frame C5 -3 %); between 2.5 and 6 a longer
-  // one, ceil(frames / 4) (below); Renderer.tune tries equal blocks and both.
-  int fpl_head = fpl;
-  A.nb_head = INT32_MAX;  // every block fpl frames
-  A.fpl_tail = fpl;
-  // Auto: ceil(frames / 8) from 6 pixels per lane; from 2.5, on a whole image (one
-  // stripe set), ceil(frames / 4): C2 and C3 at 4 pixels per lane, 20 frames: 9.00 /
-  // 2.98 ms against equal blocks' 9.34 / 3.08 (and (17, 3) 9.24 / 3.02); a strong-scaled
-  // share keeps equal blocks (the C5 4-rank share: 43.1 ms with (15, 5), 40.4 equal;
-  // profiles/r04_last_block_auto.jsonl)
-  const bool tail_auto = T.last_block_frames == 0 && (slots_per_px >= 6.0 || p->stripe_count == 1);
-  if (tail_ok && n_launch == 1 && n_blocks_all >= 2 && (T.last_block_frames > 0 || tail_auto)) {
-    const int nb = (int)n_blocks_all;
-    const int L = T.last_block_frames > 0 ? T.last_block_frames
-                                          : (slots_per_px >= 6.0 ? (p->frames + 7) / 8 : (p->frames + 3) / 4);
-    if (L < fpl) {
-      const int head = (p->frames - L + nb - 2) / (nb - 1);
-      const int last = p->frames - (nb - 1) * head;
-      if (last >= 1 && last <= L && head <= cap) {  // the head blocks keep the block cap
-        fpl_head = head;
-        A.nb_head = nb - 1;
-        A.fpl_tail = last;
-      }
-    }
-  }
-  if (n_launch + 1 > ctx->queue_cap) {  // kQueues heads per launch (+ the primary pass), zeroed by memsets
-    if (ctx->d_queue) HIP_OK(hipFree(ctx->d_queue));
-    ctx->d_queue = nullptr;
-    ctx->queue_cap = 0;
-    const int cap = std::max(n_launch + 1, 64);
-    HIP_OK(hipMalloc(&ctx->d_queue, (size_t)cap * kQueues * kQueueStride * sizeof(uint32_t)));
-    ctx->queue_cap = cap;
-  }
-  const int64_t n_px = (int64_t)p->width * p->height;
-  if (max_blocks > 1 && n_blocks_all > 1 && n_px > ctx->handoff_cap) {
-    if (ctx->d_handoff) HIP_OK(hipFree(ctx->d_handoff));
-    ctx->d_handoff = nullptr;
-    ctx->handoff_cap = 0;
-    const size_t bytes = (size_t)n_px * kHandoffWords * sizeof(unsigned long long);
-    HIP_OK(hipMalloc(&ctx->d_handoff, bytes));
-    HIP_OK(hipMemsetAsync(ctx->d_handoff, 0, bytes, st));  // tag 0 never matches (blocks >= 1)
-    ctx->handoff_cap = n_px;
-  }
-  A.fpl = fpl_head;
-  A.handoff = ctx->d_handoff;
-  A.spill = ctx->d_spill;
-  A.wave_log = nullptr;
-  const bool px_fit = ctx->stats_on && n_px <= ctx->px_cap;  // never past the caller's buffers
-  A.px_segments = px_fit ? ctx->px_segments : nullptr;
-  A.px_iters = px_fit ? ctx->px_iters : nullptr;
-  A.prim_cost = nullptr;  // set where the primary-hit pass runs
-  ctx->wave_log_n = 0;
-  if (kTiming) {  // diagnostics: each launch's workgroups log their timeline (the last launch's remain)
-    if (grid > ctx->wave_log_cap) {
-      if (ctx->d_wave_log) HIP_OK(hipFree(ctx->d_wave_log));
-      ctx->d_wave_log = nullptr;
-      ctx->wave_log_cap = 0;
-      HIP_OK(hipMalloc(&ctx->d_wave_log, (size_t)grid * kWaveLogWords * sizeof(unsigned long long)));
-      ctx->wave_log_cap = grid;
-    }
-    A.wave_log = ctx->d_wave_log;
-    ctx->wave_log_n = grid;
-  }
-  // pixel_spread auto: spread slots up to 2.5 pixels per resident lane, where
-  // each pixel's own chain sets the time (an N-rank share).  Tile-major slots
-  // put one tile's dear pixels (C2: the pitcher's inside, ~29 loop iterations
-  // per segment) in one wave, whose iterations then run the union of their
-  // phases; spread, they share waves with cheap pixels that finish early.
-  // Slowest share of 8 ranks: C2 5.83 -> 4.20 ms, C4 (64 frames) 58.1 -> 50.9;
-  // 4 ranks: C2 6.51 -> 5.22, C4 76.7 -> 73.0; whole images even (C2, C3, C4,
-  // C5 within 0.7 %; profiles/r04_spread.jsonl).
-  A.spread = T.pixel_spread == 2 || (T.pixel_spread == 0 && px_per_lane <= 2.5) ? 1 : 0;
-  A.entry_log = nullptr;
-  ctx->entry_log_n = 0;
-  if (kTiming && n_launch == 1 && (int64_t)p->width * p->height * n_blocks_all <= (16ll << 20)) {
-    const int64_t need = (int64_t)p->width * p->height * n_blocks_all;
-    if (need > ctx->entry_log_cap) {
-      if (ctx->d_entry_log) HIP_OK(hipFree(ctx->d_entry_log));
-      ctx->d_entry_log = nullptr;
-      ctx->entry_log_cap = 0;
-      HIP_OK(hipMalloc(&ctx->d_entry_log, (size_t)need * 3 * sizeof(uint32_t)));
-      ctx->entry_log_cap = need;
-    }
+  return MCPT_OK;
+}
+
+// The spill areas of `grid_wg` workgroups (spill_stride entries per lane; 0 without the window).
+static int ensure_spill(mcpt_ctx *ctx, int64_t grid_wg, const RenderArgs &A) {
+  return grow_dev(ctx->spill_cap, grid_wg * kWgWaves * 64 * A.spill_stride, (void **)&ctx->d_spill, sizeof(int32_t));
+}
+
+// Diagnostics (kTiming): each launch's workgroups log their timeline (the
+// last launch's remain), and a one-launch call logs every (pixel, block) entry.
+static int ensure_diag_buffers(mcpt_ctx *ctx, const mcpt_render_params *p, const mcpt::PlanOut &P, hipStream_t st,
+                               RenderArgs &A) {
+  A.wave_log = nullptr, A.entry_log = nullptr;
+  ctx->wave_log_n = ctx->entry_log_n = 0;
+  if (!kTiming) return MCPT_OK;
+  const int64_t grid = P.grid_wg * kWgWaves;
+  MCPT_TRY(grow_dev(ctx->wave_log_cap, grid, (void **)&ctx->d_wave_log, kWaveLogWords * sizeof(unsigned long long)));
+  A.wave_log = ctx->d_wave_log;
+  ctx->wave_log_n = grid;
+  const int64_t need = (int64_t)p->width * p->height * P.n_blocks_all;
+  if (P.n_launch == 1 && need <= (16ll << 20)) {
+    MCPT_TRY(grow_dev(ctx->entry_log_cap, need, (void **)&ctx->d_entry_log, 3 * sizeof(uint32_t)));
     HIP_OK(hipMemsetAsync(ctx->d_entry_log, 0, (size_t)need * 3 * sizeof(uint32_t), st));
     A.entry_log = ctx->d_entry_log;
     ctx->entry_log_n = need;
-    ctx->entry_log_blocks = (int32_t)n_blocks_all;
+    ctx->entry_log_blocks = (int32_t)P.n_blocks_all;
   }
+  return MCPT_OK;
+}
+
+// The dearest-first tile order, built from the primary-hit pass's per-pixel
+// costs once per primary-hit cache (`fresh`: this call computed it) and order mode.
+static int tile_order(mcpt_ctx *ctx, int64_t tiles, bool fresh, hipStream_t st, RenderArgs &A) {
+  if (ctx->tune.tile_order == 1) return MCPT_OK;                              // tuning value 1: off
+  const int32_t mode = ctx->tune.tile_order == 0 ? 1 : ctx->tune.tile_order;  // 1 max, 2 sum
+  if (fresh || ctx->tile_order_mode != mode) {
+    MCPT_TRY(grow_dev(ctx->tile_cap, tiles, (void **)&ctx->d_tile_order, sizeof(int32_t), (void **)&ctx->d_tile_key, 1));
+    hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)tiles), dim3(64), 0, st, A, ctx->d_prim_cost, (int32_t)tiles,
+                       mode == 2 ? 1 : 0, ctx->d_tile_key);
+    hipLaunchKernelGGL(k_tile_sort, dim3(1), dim3(1024), 0, st, ctx->d_tile_key, (int32_t)tiles, ctx->d_tile_order);
+    HIP_OK(hipGetLastError());
+    ctx->tile_order_mode = mode;
+  }
+  A.tile_order = ctx->d_tile_order;
+  return MCPT_OK;
+}
+
+// The primary-hit pass into ctx->d_prim: k_primary on small trees, k_render's
+// PRIM form beyond (kPrimSmallTree).
+static int primary_pass(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_render_params *p, const KernelChoice &K,
+                        const mcpt::PlanOut &P, hipStream_t st, RenderArgs &A) {
+  const int64_t n_px = (int64_t)p->width * p->height;
+  if (n_px > ctx->prim_cap) ctx->prim_valid = false;
+  MCPT_TRY(grow_dev(ctx->prim_cap, n_px, (void **)&ctx->d_prim, sizeof(PrimHit), (void **)&ctx->d_prim_cost,
+                    sizeof(uint32_t)));
+  A.prim_cost = ctx->d_prim_cost;
+  // the pass writes its own stripes' costs only: zero the others, so
+  // the tile keys and mcpt_get_primary_cost never read stale words
+  if (p->stripe_count > 1) HIP_OK(hipMemsetAsync(ctx->d_prim_cost, 0, (size_t)n_px * sizeof(uint32_t), st));
+  if (scene->near4_bytes <= kPrimSmallTree) {
+    // small trees: one ray per lane, one 8x8 tile per workgroup
+    const size_t lds_p = (size_t)K.depth_entries * 64 * sizeof(int32_t);
+    const dim3 g((unsigned)P.tiles);
+    if (p->mode == MCPT_MODE_NOPRUNE)
+      hipLaunchKernelGGL(k_primary<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim);
+    else
+      hipLaunchKernelGGL(k_primary<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim);
+    HIP_OK(hipGetLastError());
+    return MCPT_OK;
+  }
+  // the same persistent machine in its PRIM form: one frame, no state;
+  // its own queue heads (the slot after the render launches')
+  RenderArgs Ap = A;
+  Ap.frame_begin = 0;
+  Ap.frames = Ap.fpl = Ap.blocks = Ap.fpl_tail = 1;
+  Ap.nb_head = INT32_MAX;
+  Ap.prim = nullptr;
+  Ap.prim_out = ctx->d_prim;
+  Ap.wave_log = nullptr;
+  Ap.px_segments = Ap.px_iters = Ap.entry_log = nullptr;
+  Ap.spread = 0;  // coherent primary rays: tile-major slots (spread measured slower here)
+  Ap.queue = ctx->d_queue + (size_t)P.n_launch * kQueues * kQueueStride;
+  HIP_OK(hipMemsetAsync(Ap.queue, 0, (size_t)kQueues * kQueueStride * sizeof(uint32_t), st));
+  // its own resident grid: the PRIM form needs fewer registers
+  int per_cu_p = 0;
+  MCPT_TRY(occupancy(ctx, K.prim_fn, K.lds, &per_cu_p));
+  const int64_t grid_pwg = std::max<int64_t>(
+      1, std::min<int64_t>((P.tiles + kWgWaves - 1) / kWgWaves, (int64_t)std::max(per_cu_p, 1) * ctx->n_cu));
+  MCPT_TRY(ensure_spill(ctx, grid_pwg, A));
+  A.spill = Ap.spill = ctx->d_spill;
+  void *pargs[] = {&Ap};
+  HIP_OK(hipLaunchKernel(K.prim_fn, dim3((unsigned)grid_pwg), dim3(64 * kWgWaves), pargs, K.lds, st));
+  return MCPT_OK;
+}
+
+// Primary-hit cache (PrimHit): computed once per (scene, camera, image,
+// stripes, mode) and kept across calls; auto (0) computes it for a call of
+// two or more frames, or for a one-frame call of the same view as the
+// previous call (the reference's one frame per update()); 1 always, 2
+// never.  Speed only: the same bits either way.  *state = mcpt_stats.primary_cache.
+static int primary_cache(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_render_params *p,
+                         const KernelChoice &K, const mcpt::PlanOut &P, hipStream_t st, RenderArgs &A, int *state) {
+  A.prim = nullptr, A.prim_out = nullptr, A.tile_order = nullptr;
+  A.prim_cost = nullptr;  // set where the primary-hit pass runs
+  *state = 0;
+  if (ctx->tune.primary_cache == 2 || P.tiles <= 0 || p->frames <= 0) return MCPT_OK;
+  PrimKey key;
+  std::memset(&key, 0, sizeof key);
+  key.scene_uid = scene->uid;
+  std::memcpy(&key.cam, cam, sizeof key.cam);
+  key.w = p->width, key.h = p->height, key.mode = p->mode;
+  key.stripe_rows = p->stripe_rows, key.stripe_index = p->stripe_index, key.stripe_count = p->stripe_count;
+  const bool have = ctx->prim_valid && std::memcmp(&key, &ctx->prim_key, sizeof key) == 0;
+  const bool again = ctx->seen_valid && std::memcmp(&key, &ctx->seen_key, sizeof key) == 0;
+  ctx->seen_key = key;
+  ctx->seen_valid = true;
+  if (!(have || ctx->tune.primary_cache == 1 || p->frames >= 2 || again)) return MCPT_OK;
+  if (!have) {
+    MCPT_TRY(primary_pass(ctx, scene, p, K, P, st, A));
+    HIP_OK(hipEventRecord(ctx->ev_prim, st));
+    ctx->prim_key = key;
+    ctx->tile_order_mode = 0;  // a new cache: the tile order is rebuilt from its costs
+    ctx->prim_valid = true;
+  }
+  A.prim = ctx->d_prim;
+  *state = have ? 1 : 2;
+  return tile_order(ctx, P.tiles, !have, st, A);
+}
+
+// The render launches: P.max_blocks blocks of P.fpl frames each at most.
+static int launch_blocks(mcpt_ctx *ctx, const mcpt_render_params *p, const KernelChoice &K, const mcpt::PlanOut &P,
+                         hipStream_t st, RenderArgs &A, int *launches) {
+  *launches = 0;
+  if (P.tiles <= 0 || p->frames <= 0) return MCPT_OK;
+  HIP_OK(hipMemsetAsync(ctx->d_queue, 0, (size_t)P.n_launch * kQueues * kQueueStride * sizeof(uint32_t), st));
+  for (int64_t f0 = 0; f0 < p->frames; f0 += P.max_blocks * P.fpl) {
+    A.frame_begin = p->frame_begin + (int32_t)f0;
+    A.frames = (int32_t)std::min<int64_t>(P.max_blocks * P.fpl, p->frames - f0);
+    A.blocks = (A.frames + P.fpl - 1) / P.fpl;
+    A.queue = ctx->d_queue + (size_t)*launches * kQueues * kQueueStride;
+    // a fresh tag per launch: granules of earlier launches never match.
+    // After 255 launches the 8-bit launch tags wrap; the granules are
+    // cleared then (stream-ordered before this launch), so every granule in
+    // the area was written during the current cycle of tags.
+    if (((++ctx->launch_seq) & 0xFFu) == 0) {
+      ++ctx->launch_seq;
+      if (ctx->d_handoff)
+        HIP_OK(hipMemsetAsync(ctx->d_handoff, 0, (size_t)ctx->handoff_cap * kHandoffWords * 8, st));
+    }
+    A.tag_base = (ctx->launch_seq & 0xFFu) << 8;
+    void *kargs[] = {&A};
+    HIP_OK(hipLaunchKernel(K.fn, dim3((unsigned)P.grid_wg), dim3(64 * kWgWaves), kargs, K.lds, st));
+    ++*launches;
+  }
+  return MCPT_OK;
+}
+
+int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_render_params *p,
+                       uint32_t *seeds, float *hist, int32_t *count, void *stream) {
+  if (!ctx || !scene || !cam || !p || !seeds || !hist || !count) return mcpt::fail(MCPT_ERR_ARG, "render: null argument");
+  MCPT_TRY(check_render(p));
+  HIP_OK(hipSetDevice(ctx->device));
+  hipStream_t st = (hipStream_t)stream;
+  RenderArgs A;
+  A.cam = *cam;
+  A.S = scene->view;
+  A.seeds = seeds;
+  A.hist = (f4 *)hist;
+  A.count = count;
+  A.stats = ctx->d_stats;
+  A.W = p->width, A.H = p->height;
+  A.stripe_rows = p->stripe_rows, A.stripe_index = p->stripe_index, A.stripe_count = p->stripe_count;
+  A.max_depth = p->max_depth, A.max_attempt = p->max_attempt;
+  // tuned (tools/sweep.py, tools/ab.py): leaf phase at >= 4 lanes
+  // (single-leaf schedule) or >= 16 (paired), shade at >= 32
+  const mcpt_tuning &T = ctx->tune;
+  const bool pair = p->schedule == MCPT_SCHED_PAIRED;
+  A.th_leaf = T.leaf_threshold > 0 ? T.leaf_threshold : (pair ? 16 : 4);
+  A.th_shade = T.shade_threshold > 0 ? T.shade_threshold : 32;
+  A.chunk = T.queue_chunk > 0 ? T.queue_chunk : 4;  // queue entries per atomic (at least)
+  A.th_fetch = T.fetch_threshold > 0 ? T.fetch_threshold : 1;
+  A.n_queues = T.queues > 0 ? (uint32_t)std::min(T.queues, kQueues) : (uint32_t)kQueues;
+  KernelChoice K;
+  MCPT_TRY(select_kernel(ctx, scene, p, A, &K));
+  // the launch plan (mcpt_plan.h): the grid, frames per block, blocks per launch
+  const mcpt::PlanOut P = mcpt::plan_launches(
+      {p->width, p->height, p->frames, p->frames_per_launch, p->stripe_rows, p->stripe_index, p->stripe_count,
+       T.block_entries, T.max_block_frames, T.last_block_frames, T.pixel_spread,
+       (int64_t)std::max(K.per_cu, 1) * ctx->n_cu, kWgWaves});
+  A.local_rows = P.local_rows, A.tiles_x = P.tiles_x, A.spread = P.spread;
+  A.fpl = P.fpl_head, A.nb_head = P.nb_head, A.fpl_tail = P.fpl_tail;
+  // spill areas; kQueues heads per launch (+ the primary pass), zeroed by memsets; hand-off granules
+  MCPT_TRY(ensure_spill(ctx, P.grid_wg, A));
+  MCPT_TRY(grow_dev(ctx->queue_cap, std::max(P.n_launch + 1, 64), (void **)&ctx->d_queue,
+                (size_t)kQueues * kQueueStride * sizeof(uint32_t)));
+  const int64_t n_px = (int64_t)p->width * p->height;
+  if (P.max_blocks > 1 && P.n_blocks_all > 1 && n_px > ctx->handoff_cap) {
+    const size_t granules = kHandoffWords * sizeof(unsigned long long);
+    MCPT_TRY(grow_dev(ctx->handoff_cap, n_px, (void **)&ctx->d_handoff, granules));
+    const hipError_t cleared = hipMemsetAsync(ctx->d_handoff, 0, (size_t)n_px * granules, st);  // tag 0 never matches
+    if (cleared != hipSuccess) ctx->handoff_cap = 0;  // grown and cleared again by the next call
+    HIP_OK(cleared);
+  }
+  A.handoff = ctx->d_handoff;
+  A.spill = ctx->d_spill;
+  const bool px_fit = ctx->stats_on && n_px <= ctx->px_cap;  // never past the caller's buffers
+  A.px_segments = px_fit ? ctx->px_segments : nullptr;
+  A.px_iters = px_fit ? ctx->px_iters : nullptr;
+  MCPT_TRY(ensure_diag_buffers(ctx, p, P, st, A));
   if (ctx->stats_on || kDebug || kTiming)
     HIP_OK(hipMemsetAsync(ctx->d_stats, 0, kStatSlots * sizeof(unsigned long long), st));
   HIP_OK(hipEventRecord(ctx->ev0, st));
-  // primary-hit cache (PrimHit): computed once per (scene, camera, image,
-  // stripes, mode) and kept across calls; auto (0) computes it for a call of
-  // two or more frames, or for a one-frame call of the same view as the
-  // previous call (the reference's one frame per update()); 1 always, 2
-  // never.  Speed only: the same bits either way.
-  A.prim = nullptr;
-  A.prim_out = nullptr;
-  A.tile_order = nullptr;
-  int prim_state = 0;
-  if (T.primary_cache != 2 && tiles > 0 && p->frames > 0) {
-    PrimKey key;
-    std::memset(&key, 0, sizeof key);
-    key.scene_uid = scene->uid;
-    std::memcpy(&key.cam, cam, sizeof key.cam);
-    key.w = p->width;
-    key.h = p->height;
-    key.stripe_rows = p->stripe_rows;
-    key.stripe_index = p->stripe_index;
-    key.stripe_count = p->stripe_count;
-    key.mode = p->mode;
-    const bool have = ctx->prim_valid && std::memcmp(&key, &ctx->prim_key, sizeof key) == 0;
-    const bool again = ctx->seen_valid && std::memcmp(&key, &ctx->seen_key, sizeof key) == 0;
-    ctx->seen_key = key;
-    ctx->seen_valid = true;
-    if (have || T.primary_cache == 1 || p->frames >= 2 || again) {
-      if (!have) {
-        const int64_t n_px = (int64_t)p->width * p->height;
-        if (n_px > ctx->prim_cap) {
-          ctx->prim_valid = false;
-          if (ctx->d_prim) HIP_OK(hipFree(ctx->d_prim));
-          if (ctx->d_prim_cost) HIP_OK(hipFree(ctx->d_prim_cost));
-          ctx->d_prim = nullptr;
-          ctx->d_prim_cost = nullptr;
-          ctx->prim_cap = 0;
-          HIP_OK(hipMalloc(&ctx->d_prim, (size_t)n_px * sizeof(PrimHit)));
-          HIP_OK(hipMalloc(&ctx->d_prim_cost, (size_t)n_px * sizeof(uint32_t)));
-          ctx->prim_cap = n_px;
-        }
-        A.prim_cost = ctx->d_prim_cost;
-        // the pass writes its own stripes' costs only: zero the others, so
-        // the tile keys and mcpt_get_primary_cost never read stale words
-        if (p->stripe_count > 1) HIP_OK(hipMemsetAsync(ctx->d_prim_cost, 0, (size_t)n_px * sizeof(uint32_t), st));
-        if (scene->near4_bytes <= kPrimSmallTree) {
-          // small trees: one ray per lane, one 8x8 tile per workgroup
-          const size_t lds_p = (size_t)depth_entries * 64 * sizeof(int32_t);
-          const dim3 g((unsigned)tiles);
-          if (noprune)
-            hipLaunchKernelGGL(k_primary<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim);
-          else
-            hipLaunchKernelGGL(k_primary<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim);
-          HIP_OK(hipGetLastError());
-        } else {
-          // the same persistent machine in its PRIM form: one frame, no state;
-          // its own queue heads (the slot after the render launches')
-          RenderArgs Ap = A;
-          Ap.frame_begin = 0;
-          Ap.frames = 1;
-          Ap.fpl = 1;
-          Ap.blocks = 1;
-          Ap.nb_head = INT32_MAX;
-          Ap.fpl_tail = 1;
-          Ap.prim = nullptr;
-          Ap.prim_out = ctx->d_prim;
-          Ap.wave_log = nullptr;
-          Ap.px_segments = nullptr;
-          Ap.px_iters = nullptr;
-          Ap.entry_log = nullptr;
-          Ap.spread = 0;  // coherent primary rays: tile-major slots (spread measured slower here)
-          Ap.queue = ctx->d_queue + (size_t)n_launch * kQueues * kQueueStride;
-          HIP_OK(hipMemsetAsync(Ap.queue, 0, (size_t)kQueues * kQueueStride * sizeof(uint32_t), st));
-          // its own resident grid: the PRIM form needs fewer registers
-          const void *pfn = kpfns[kind][win][pair];
-          int per_cu_p = 0;
-          rc = occupancy(ctx, pfn, lds, &per_cu_p);
-          if (rc) return rc;
-          const int64_t grid_pwg = std::max<int64_t>(
-              1, std::min<int64_t>((tiles + kWgWaves - 1) / kWgWaves, (int64_t)std::max(per_cu_p, 1) * ctx->n_cu));
-          const int64_t spill_p = win ? grid_pwg * kWgWaves * 64 * (int64_t)A.spill_stride : 0;
-          if (spill_p > ctx->spill_cap) {
-            if (ctx->d_spill) HIP_OK(hipFree(ctx->d_spill));
-            ctx->d_spill = nullptr;
-            ctx->spill_cap = 0;
-            HIP_OK(hipMalloc(&ctx->d_spill, (size_t)spill_p * sizeof(int32_t)));
-            ctx->spill_cap = spill_p;
-            A.spill = ctx->d_spill;
-          }
-          Ap.spill = ctx->d_spill;
-          void *pargs[] = {&Ap};
-          HIP_OK(hipLaunchKernel(pfn, dim3((unsigned)grid_pwg), dim3(64 * kWgWaves), pargs, lds, st));
-        }
-        HIP_OK(hipEventRecord(ctx->ev_prim, st));
-        ctx->prim_key = key;
-        ctx->tile_order_mode = 0;  // a new cache: the tile order is rebuilt from its costs
-        ctx->prim_valid = true;
-      }
-      A.prim = ctx->d_prim;
-      prim_state = have ? 1 : 2;
-      // the dearest-first tile order, built from the pass's per-pixel costs
-      // once per primary-hit cache (and order mode)
-      const int32_t mode = T.tile_order == 0 ? 1 : T.tile_order;  // 1 max, 2 sum (tuning value 1: off)
-      if (T.tile_order != 1) {
-        if (!have || ctx->tile_order_mode != mode) {
-          if (tiles > ctx->tile_cap) {
-            if (ctx->d_tile_order) HIP_OK(hipFree(ctx->d_tile_order));
-            if (ctx->d_tile_key) HIP_OK(hipFree(ctx->d_tile_key));
-            ctx->d_tile_order = nullptr;
-            ctx->d_tile_key = nullptr;
-            ctx->tile_cap = 0;
-            HIP_OK(hipMalloc(&ctx->d_tile_order, (size_t)tiles * sizeof(int32_t)));
-            HIP_OK(hipMalloc(&ctx->d_tile_key, (size_t)tiles));
-            ctx->tile_cap = tiles;
-          }
-          hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)tiles), dim3(64), 0, st, A, ctx->d_prim_cost, (int32_t)tiles,
-                             mode == 2 ? 1 : 0, ctx->d_tile_key);
-          hipLaunchKernelGGL(k_tile_sort, dim3(1), dim3(1024), 0, st, ctx->d_tile_key, (int32_t)tiles,
-                             ctx->d_tile_order);
-          HIP_OK(hipGetLastError());
-          ctx->tile_order_mode = mode;
-        }
-        A.tile_order = ctx->d_tile_order;
-      }
-    }
-  }
-  int launches = 0;
-  if (tiles > 0 && p->frames > 0) {
-    HIP_OK(hipMemsetAsync(ctx->d_queue, 0, (size_t)n_launch * kQueues * kQueueStride * sizeof(uint32_t), st));
-    for (int64_t f0 = 0; f0 < p->frames; f0 += max_blocks * fpl) {
-      A.frame_begin = p->frame_begin + (int32_t)f0;
-      A.frames = (int32_t)std::min<int64_t>(max_blocks * fpl, p->frames - f0);
-      A.blocks = (A.frames + fpl - 1) / fpl;
-      A.queue = ctx->d_queue + (size_t)launches * kQueues * kQueueStride;
-      // a fresh tag per launch: granules of earlier launches never match.
-      // After 255 launches the 8-bit launch tags wrap; the granules are
-      // cleared then (stream-ordered before this launch), so every granule in
-      // the area was written during the current cycle of tags.
-      if (((++ctx->launch_seq) & 0xFFu) == 0) {
-        ++ctx->launch_seq;
-        if (ctx->d_handoff)
-          HIP_OK(hipMemsetAsync(ctx->d_handoff, 0, (size_t)ctx->handoff_cap * kHandoffWords * 8, st));
-      }
-      A.tag_base = (ctx->launch_seq & 0xFFu) << 8;
-      void *kargs[] = {&A};
-      HIP_OK(hipLaunchKernel(kfn, dim3((unsigned)grid_wg), dim3(64 * kWgWaves), kargs, lds, st));
-      ++launches;
-    }
-  }
+  int prim_state = 0, launches = 0;
+  MCPT_TRY(primary_cache(ctx, scene, cam, p, K, P, st, A, &prim_state));
+  MCPT_TRY(launch_blocks(ctx, p, K, P, st, A, &launches));
   HIP_OK(hipEventRecord(ctx->ev1, st));
   // asynchronous: mcpt_get_stats waits for ev1 and reads the time and counters
   std::memset(&ctx->last, 0, sizeof(ctx->last));
-  ctx->last.launches = launches;
-  ctx->last.frames_per_block = fpl_head;
-  ctx->last.stack_window = win ? 1 : 0;
-  ctx->last.quantized = kind == 2 ? 1 : 0;
-  ctx->last.top_levels = A.top_levels;
-  ctx->last.workgroups = (int32_t)grid;
-  ctx->last.primary_cache = prim_state;
+  ctx->last.launches = launches, ctx->last.frames_per_block = P.fpl_head, ctx->last.primary_cache = prim_state;
+  ctx->last.stack_window = K.win ? 1 : 0, ctx->last.quantized = K.kind == 2 ? 1 : 0;
+  ctx->last.top_levels = A.top_levels, ctx->last.workgroups = (int32_t)(P.grid_wg * kWgWaves);
   ctx->last_pending = true;
   ctx->last_stats = ctx->stats_on || kDebug || kTiming;
   return MCPT_OK;

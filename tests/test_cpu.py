@@ -344,6 +344,22 @@ def test_sah_search_tree_invariants(sah_check_exe, n, seed, clustered):
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
 
 
+def test_launch_plan_cases(tmp_path):
+    """The launch planner (csrc/mcpt_plan.h: rows and tiles of a stripe share,
+    the grid, frames per block, the short last block, blocks per launch, the
+    hand-off limit, the spread rule) gives the recorded plan for every case of
+    tests/golden/plan_cases.txt (tests/native/plan_check.cpp)."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "montecarlopathtracing_amd", "csrc")
+    exe = str(tmp_path / "plan_check")  # the header alone: no HIP, no library
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I", csrc, os.path.join(root, "tests", "native", "plan_check.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe, os.path.join(root, "tests", "golden", "plan_cases.txt")], capture_output=True, text=True,
+                         timeout=60)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+
+
 # ------------------------------------------------- treelet restructuring
 def _sah_metric(nodes):
     """BVH::TEST::SAH (bvhtest.cpp:97-108), in double like the reference."""
