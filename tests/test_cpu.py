@@ -360,6 +360,24 @@ def test_launch_plan_cases(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
 
 
+def test_queue_protocol(tmp_path):
+    """k_render's queue and hand-off arithmetic (csrc/mcpt_queue.h), walked
+    exhaustively at small shapes (tests/native/queue_check.cpp): every queue
+    entry of a launch maps to one pixel of this rank's rows, once per block,
+    a pixel's blocks in one queue at one slot in order; every block of every
+    launch of a plan has at least one frame, blocks abut and launches add up
+    to the call; the hand-off record round-trips bit for bit and is ready only
+    under its own tag; the wave's queue state visits every queue once."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "montecarlopathtracing_amd", "csrc")
+    exe = str(tmp_path / "queue_check")  # the two headers alone: no HIP, no library
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I", csrc, os.path.join(root, "tests", "native", "queue_check.cpp"),
+                    "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.startswith("ok"), out.stdout + out.stderr
+
+
 # ------------------------------------------------- treelet restructuring
 def _sah_metric(nodes):
     """BVH::TEST::SAH (bvhtest.cpp:97-108), in double like the reference."""
