@@ -129,6 +129,11 @@ typedef struct mcpt_render_params {
                                        max_block_frames frames per launch */
   int32_t schedule;                 /* MCPT_SCHED_*: how k_render batches leaf
                                        tests (results identical; speed only) */
+  int32_t jitter;                   /* 0 (a zero-initialised struct): every frame
+                                       shoots the reference's ray through the
+                                       pixel's corner; 1: sub-pixel jitter
+                                       (antialiasing, see mcpt_render_frames);
+                                       any other value is MCPT_ERR_ARG        */
 } mcpt_render_params;
 
 /* Leaf-test schedules of the fused kernel (bit-identical results):
@@ -174,7 +179,8 @@ typedef struct mcpt_stats {
                                        quantized tree (EXACT mode)            */
   int32_t  primary_cache;           /* 0: the last call traced every frame's
                                        primary ray; 1: it read the cached
-                                       primary hits; 2: it computed them too  */
+                                       primary hits; 2: it computed them too
+                                       (always 0 for a jittered call)         */
   double   primary_ms;              /* primary_cache 2: device time of the
                                        primary-hit pass (part of kernel_ms)   */
   int32_t  top_levels;              /* the search tree's top levels the last
@@ -214,7 +220,8 @@ typedef struct mcpt_tuning {
                                (a call of >= 2 frames, or a one-frame call of
                                the previous call's view, computes it; every
                                call with a matching one reads it), 1 always,
-                               2 never                                          */
+                               2 never; a jittered call (mcpt_render_params
+                               .jitter) neither reads nor builds it             */
   int32_t last_block_frames; /* auto frames-per-block, one-launch calls of two
                                or more blocks: the last block of every pixel
                                is this many frames and the others share the
@@ -250,10 +257,11 @@ typedef struct mcpt_tuning {
  * arguments (3: mcpt_tuning's tile_order / pixel_spread,
  * mcpt_set_pixel_segments' capacity; 4: the rejected T-phase-helper and
  * merged-gather knobs and counters removed from mcpt_tuning / mcpt_stats,
- * `top_levels` added to both).
+ * `top_levels` added to both; 5: `jitter` appended to mcpt_render_params,
+ * mcpt_generate_rays_jittered added).
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
-#define MCPT_ABI_VERSION 4
+#define MCPT_ABI_VERSION 5
 int32_t mcpt_abi_version(void);
 const char *mcpt_version(void);
 const char *mcpt_last_error(void);
@@ -342,7 +350,17 @@ int mcpt_scene_read(const mcpt_scene *scene, int32_t which, void *host, int64_t 
  * Stream-ordered and asynchronous: the call enqueues its work on `stream`
  * and returns (mcpt_get_stats waits for it).  One stream per context at a
  * time: the context's queue heads and hand-off area are reused by every
- * call.                                                                  */
+ * call.
+ * params->jitter = 1 (opt-in antialiasing, no reference counterpart): every
+ * frame of a pixel starts with two draws from the pixel's own seed chain,
+ * before any shading draw of that frame, jx = lcg15(seed) * 2^-15 and then jy
+ * the same, and generateRay runs with px = ((float)idx + jx) / width,
+ * py = ((float)idy + jy) / height, everything after unchanged: a box filter
+ * over the pixel's footprint whose jx = jy = 0 corner is the reference's ray.
+ * The history rule is untouched: a jittered pixel is still the reference's
+ * mean over its non-zero samples.  Such a call neither reads nor builds the
+ * primary-hit cache (mcpt_stats.primary_cache = 0) and leaves a held one
+ * valid for later unjittered calls.                                      */
 int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam,
                        const mcpt_render_params *params, uint32_t *seeds_dev,
                        float *hist_dev, int32_t *count_dev, void *stream);
@@ -379,6 +397,11 @@ int mcpt_state_destroy(mcpt_state *st);
 /* rayGenerator.cl generateRay (W x H NDRange)                            */
 int mcpt_generate_rays(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t width, int32_t height,
                        mcpt_ray *rays_dev, void *stream);
+/* The same with a jittered render's sub-pixel offsets (mcpt_render_frames,
+ * params->jitter): pixel (idx, idy) takes its two draws from, and writes the
+ * advanced seed back to, seeds_dev[idy * width + idx].                     */
+int mcpt_generate_rays_jittered(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t width, int32_t height,
+                                uint32_t *seeds_dev, mcpt_ray *rays_dev, void *stream);
 /* intersect.cl intersectRays (tmin = EPSILON 1e-3, oclbasic.h:193)        */
 int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays_dev,
                    int64_t n, mcpt_hit *hits_dev, float tmin, int32_t mode, void *stream);

@@ -1,7 +1,7 @@
 """Command line: render a reference config.json on the GPU(s) and write the .hdr,
 or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
-    python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG]
+    python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -10,14 +10,20 @@ import sys
 import time
 
 
-def main(argv=None):
+def parser():
     ap = argparse.ArgumentParser(prog="montecarlopathtracing_amd")
     ap.add_argument("config", nargs="?", default="config.json")
     ap.add_argument("--configid", type=int, default=None)
     ap.add_argument("--out", default=".")
     ap.add_argument("--frames", type=int, default=None, help="override attempt+1 frames")
     ap.add_argument("--preview", default=None, help="also write the gamma-2.2 display image (testkernel.cl) as PNG")
-    a = ap.parse_args(argv)
+    ap.add_argument("--jitter", action="store_true",
+                    help="sub-pixel jitter (antialiasing) even if the config entry has no \"jitter\": true")
+    return ap
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
     from . import config as C
     cfg = C.Config(a.config, a.configid)
     if cfg.TESTALL() or cfg.TESTBVH():
@@ -28,7 +34,7 @@ def main(argv=None):
     if ws > 1:
         return _main_dist(a)
     from .app import App
-    app = App(a.config, a.configid, out_dir=a.out)
+    app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None)
     t0 = time.time()
     if a.frames:
         app.update(a.frames)
@@ -74,7 +80,7 @@ def _main_dist(a):
     w, h = cfg.WIDTH(), cfg.HEIGHT()
     frames = a.frames or cfg.MAXATTEPMT() + 1
     out = D.render_distributed(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, cfg.MAXDEPTH(), cfg.MAXATTEPMT(),
-                               frames, R.default_seeds(w * h))
+                               frames, R.default_seeds(w * h), jitter=a.jitter or cfg.JITTER())
     if dist.get_rank() == 0:
         path = os.path.join(a.out, cfg.GETOBJNAME() + ".hdr")
         S.write_hdr(path, out[0].reshape(h, w, 4), flip=True)

@@ -28,7 +28,7 @@ BVHNODE = np.dtype([("bbmin", "<f4", 4), ("bbmax", "<f4", 4), ("pad", "<f4", 4),
 for _dt, _sz in ((CAMERA, 80), (RAY, 48), (HIT, 48), (TRIANGLE, 64), (MATERIAL, 48), (BVHNODE, 64)):
     assert _dt.itemsize == _sz
 
-ABI_VERSION = 4  # include/mcpt_hip.h MCPT_ABI_VERSION
+ABI_VERSION = 5  # include/mcpt_hip.h MCPT_ABI_VERSION
 MCPT_DIFFUSE, MCPT_GLOSSY, MCPT_TRANSPARENT, MCPT_LIGHT = 1, 2, 3, 4
 MODE_EXACT, MODE_NOPRUNE = 0, 1
 SCHED_SINGLE, SCHED_PAIRED = 0, 1  # mcpt_render_params.schedule
@@ -38,7 +38,7 @@ TERMINATED = 0xFF000000
 class RenderParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "width", "height", "max_depth", "max_attempt", "frame_begin", "frames", "stripe_rows",
-        "stripe_index", "stripe_count", "mode", "frames_per_launch", "schedule")]
+        "stripe_index", "stripe_count", "mode", "frames_per_launch", "schedule", "jitter")]
 
 
 class Stats(ctypes.Structure):
@@ -95,6 +95,7 @@ SIGNATURES = {
     "mcpt_scene_read": (_I32, [_P, _I32, _P, _I64, _P]),
     "mcpt_render_frames": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "mcpt_generate_rays": (_I32, [_P, _P, _I32, _I32, _P, _P]),
+    "mcpt_generate_rays_jittered": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
     "mcpt_intersect": (_I32, [_P, _P, _P, _I64, _P, _F32, _I32, _P]),
     "mcpt_shade": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "mcpt_accumulate": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),

@@ -7,6 +7,11 @@
 Frame semantics kept: frames 0..attempt run the history kernel (attemptCount
 <= MAX_ATTEMPT), the .hdr is written once after that from the accumulated
 frameBuffer, vertically flipped like stbi_flip_vertically_on_write(true).
+
+Extension: a config entry with "jitter": true (or App(..., jitter=True), the
+command line's --jitter) renders with sub-pixel jitter, every frame's primary
+ray through a drawn point of its pixel's footprint (antialiasing); the
+reference has none, and the default keeps its corner ray bit for bit.
 """
 import os
 
@@ -41,7 +46,7 @@ def config_scene(cfg, root, device=0, material_override=None):
 
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
-                 material_override=None):
+                 material_override=None, jitter=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -54,6 +59,7 @@ class App:
         self.material_override = material_override
         if material_override is None and self.cfg.entry.get("materials") == "diffuse_only":
             self.material_override = S.diffuse_only
+        self.jitter = self.cfg.JITTER() if jitter is None else bool(jitter)  # None: the entry's "jitter" key
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -88,11 +94,13 @@ class App:
             # blocks whatever block_entries says, and the tile order mostly shortens a launch's tail, so
             # one-block trials of either would tune a regime the run never enters.
             self.renderer.tune(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, frames=16,
-                               block_entries=None, last_block=False, tile_orders=None, frames_per_launch=16)
+                               block_entries=None, last_block=False, tile_orders=None, frames_per_launch=16,
+                               jitter=self.jitter)
             self._tuned = True
         while todo > 0:
             n = todo if self.attempt_count > att else min(todo, att + 1 - self.attempt_count)
-            self.renderer.render_frames(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, n)
+            self.renderer.render_frames(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, n,
+                                        jitter=self.jitter)
             self.attempt_count += n
             todo -= n
             if self.attempt_count > att and self.dumped is None:

@@ -52,6 +52,11 @@ class Config:
         self.bvhtype = c.get("bvhtype", "") or "hlbvh"
         self.testall = bool(c.get("testall", False))
         self.directory = c.get("directory", "")
+        # extension key (no reference counterpart; like "materials": "diffuse_only"):
+        # "jitter": true renders with sub-pixel jitter (antialiasing)
+        self.jitter = c.get("jitter", False)
+        if not isinstance(self.jitter, bool):
+            raise ValueError('config "jitter" must be true or false, got %r' % (self.jitter,))
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -92,3 +97,4 @@ class Config:
     def TESTALL(self): return self.testall
     def USEOPENCL(self): return self.opencl
     def GETOBJS(self): return self.objs
+    def JITTER(self): return self.jitter  # extension: sub-pixel jitter of the render path

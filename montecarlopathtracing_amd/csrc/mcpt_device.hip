@@ -16,6 +16,8 @@
 //  * k_generate / k_intersect / k_shade / k_accumulate — one kernel per
 //    reference kernel on the reference's AoS records, for drop-in use and for
 //    kernel-level parity with the reference code objects.
+//  * k_generate_jittered and k_render's J form — opt-in sub-pixel jitter
+//    (antialiasing), the one thing here without a reference counterpart.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -563,10 +565,18 @@ __device__ inline CamConst cam_const(const mcpt_camera &cam, uint32_t w, uint32_
   c.distance = 0.5f / cl_tan(cam.arg / 2);
   return c;
 }
+// J: the sub-pixel jitter of an opt-in antialiased render (no reference
+// counterpart): the sample sits at (idx + jx, idy + jy), jx, jy in [0, 1), a
+// box filter over the pixel's footprint whose jx = jy = 0 corner is the
+// reference's ray, bit for bit ((float)idx + 0.0f is exact).  Everything after
+// px, py is shared.
+template <bool J = false>
 __device__ inline void gen_ray_px(const mcpt_camera &cam, CamConst cc, uint32_t idx, uint32_t idy, uint32_t w,
-                                  uint32_t h, f4 &o, f4 &dir) {
+                                  uint32_t h, f4 &o, f4 &dir, float jx = 0.0f, float jy = 0.0f) {
   size_t width = w, height = h;
-  float px = ((float)idx) / width, py = (float)idy / height;
+  float sx = (float)idx, sy = (float)idy;
+  if (J) sx += jx, sy += jy;
+  float px = sx / width, py = sy / height;
   const f4 cdir = (f4){cam.direction[0], cam.direction[1], cam.direction[2], cam.direction[3]};
   const f4 chor = (f4){cam.horizontal[0], cam.horizontal[1], cam.horizontal[2], cam.horizontal[3]};
   const f4 cup = (f4){cam.up[0], cam.up[1], cam.up[2], cam.up[3]};
@@ -589,6 +599,12 @@ __device__ inline void gen_ray_px(const mcpt_camera &cam, CamConst cc, uint32_t 
 __device__ inline void gen_ray(const mcpt_camera &cam, uint32_t idx, uint32_t idy, uint32_t w, uint32_t h,
                                f4 &o, f4 &dir) {
   gen_ray_px(cam, cam_const(cam, w, h), idx, idy, w, h, o, dir);
+}
+// A jittered frame's two draws from the pixel's seed chain, before any shading
+// draw of the frame: lcg15 * 2^-15, in [0, 1) and exact in fp32.
+__device__ inline void jitter_draw(uint32_t &seed, float &jx, float &jy) {
+  jx = lcg15(seed) * 1.0f * 0x1p-15f;
+  jy = lcg15(seed) * 1.0f * 0x1p-15f;
 }
 
 // -------------------------------------------------------------------- shade
@@ -870,10 +886,16 @@ constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193,
 // PRIM: the primary-hit pass (PrimHit) run by the same machine: one frame,
 // no pixel state; a lane traces its pixel's primary ray, stores the closest
 // hit at the S phase instead of shading, and takes the next pixel.
-template <int MODE, bool STATS, bool WIN, bool PAIR, bool Q, bool PRIM = false, bool G = true>
+// J: a jittered render (mcpt_render_params.jitter): every frame starts with
+// the sub-pixel draws from the lane's seed and traces its own primary ray; no
+// primary-hit records.  A template parameter, not a launch flag: the
+// unjittered instantiations are the code they were without it (a wave-uniform
+// flag cost some of them a VGPR).
+template <int MODE, bool STATS, bool WIN, bool PAIR, bool Q, bool PRIM = false, bool G = true, bool J = false>
 __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(RenderArgs A) {
   constexpr bool PRUNE = MODE != MCPT_MODE_NOPRUNE;
   constexpr bool LIT = MODE == MCPT_MODE_NOPRUNE;
+  static_assert(!(J && PRIM), "the primary-hit pass is the unjittered frame start's");
   static_assert(!(Q && LIT), "the quantized search tree is an EXACT-mode structure");
   extern __shared__ int32_t lds_stack[];
   const int lane = threadIdx.x & 63;
@@ -946,12 +968,17 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
   int32_t blk = 0;             // frame block of the pixel (the pending entry's block while kPend)
   f4 hist = (f4){0.0f, 0.0f, 0.0f, 0.0f};
   f4 o = hist, d = hist, color = hist;
-  auto primary = [&]() __attribute__((always_inline)) {  // no jitter: every frame re-shoots the same primary ray
+  // without jitter every frame re-shoots the same primary ray; a jittered
+  // kernel (J) draws the frame's sub-pixel offsets from the lane's seed first,
+  // and zero offsets give the unjittered ray's bits
+  auto primary = [&]() __attribute__((always_inline)) {
     const f4 c4 = U->cc;
     CamConst cc;
     cc.distance = c4.x;
     cc.ratio = c4.y;
-    gen_ray_px(U->cam, cc, pixel_x(pxy), pixel_y(pxy), (uint32_t)A.W, (uint32_t)A.H, o, d);
+    float jx = 0.0f, jy = 0.0f;
+    if constexpr (J) jitter_draw(seed, jx, jy);
+    gen_ray_px<J>(U->cam, cc, pixel_x(pxy), pixel_y(pxy), (uint32_t)A.W, (uint32_t)A.H, o, d, jx, jy);
   };
   // path / traversal state (declared with the pixel state below)
   f3 rinv = (f3){0.0f, 0.0f, 0.0f};
@@ -1009,7 +1036,7 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
   // from the pixel's record and goes straight to S
   auto begin_frame = [&]() __attribute__((always_inline)) {
     color = (f4){1.0f, 1.0f, 1.0f, 1.0f};
-    if (A.prim) {
+    if (!J && A.prim) {  // (a jittered launch has no records: A.prim is null)
       const uint32_t pid = pixel_id(pxy, A.W);
       const f4 *ph = reinterpret_cast<const f4 *>(A.prim + pid);
       const f4 h0 = ph[0], h1 = ph[1];  // nrm | t, ray xyz
@@ -1464,6 +1491,22 @@ __global__ void k_generate(mcpt_camera cam, uint32_t w, uint32_t h, mcpt_ray *ra
   f4 o, d;
   gen_ray(cam, x, y, w, h, o, d);
   mcpt_ray &r = rays[(size_t)y * w + x];
+  *(f4 *)r.origin = o;
+  *(f4 *)r.direction = d;
+}
+// generateRay with the jittered render's two draws, taken from and written
+// back to the pixel's seed (what k_render does at a jittered frame's start)
+__global__ void k_generate_jittered(mcpt_camera cam, uint32_t w, uint32_t h, uint32_t *seeds, mcpt_ray *rays) {
+  uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= w || y >= h) return;
+  const size_t id = (size_t)y * w + x;
+  uint32_t seed = seeds[id];
+  float jx, jy;
+  jitter_draw(seed, jx, jy);
+  seeds[id] = seed;
+  f4 o, d;
+  gen_ray_px<true>(cam, cam_const(cam, w, h), x, y, w, h, o, d, jx, jy);
+  mcpt_ray &r = rays[id];
   *(f4 *)r.origin = o;
   *(f4 *)r.direction = d;
 }
@@ -2381,6 +2424,7 @@ static int check_render(const mcpt_render_params *p) {
   if (p->mode != MCPT_MODE_EXACT && p->mode != MCPT_MODE_NOPRUNE) return mcpt::fail(MCPT_ERR_ARG, "render: bad mode");
   if (p->schedule != MCPT_SCHED_SINGLE && p->schedule != MCPT_SCHED_PAIRED)
     return mcpt::fail(MCPT_ERR_ARG, "render: bad schedule");
+  if (p->jitter != 0 && p->jitter != 1) return mcpt::fail(MCPT_ERR_ARG, "render: bad jitter");
   return MCPT_OK;
 }
 
@@ -2424,14 +2468,16 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
   // The stack lives in LDS; when the whole stack would allow fewer resident
   // workgroups than a kStackWindow window does, the windowed kernel runs.
   const bool noprune = p->mode == MCPT_MODE_NOPRUNE;
-  // [kind: 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized][stats][window][pair][glossy materials]
-#define MCPT_KG(M, ST, W, P, QN) {(const void *)k_render<M, ST, W, P, QN, false, false>, \
-                                  (const void *)k_render<M, ST, W, P, QN, false, true>}
-#define MCPT_KR(M, ST, W, QN) {MCPT_KG(M, ST, W, false, QN), MCPT_KG(M, ST, W, true, QN)}
-#define MCPT_KK(M, QN) {{MCPT_KR(M, false, false, QN), MCPT_KR(M, false, true, QN)}, \
-                        {MCPT_KR(M, true, false, QN), MCPT_KR(M, true, true, QN)}}
-  static const void *const kfns[3][2][2][2][2] = {MCPT_KK(MCPT_MODE_EXACT, false), MCPT_KK(MCPT_MODE_NOPRUNE, false),
-                                                  MCPT_KK(MCPT_MODE_EXACT, true)};
+  // [jitter][kind: 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized][stats][window][pair][glossy materials]
+#define MCPT_KG(M, ST, W, P, QN, J) {(const void *)k_render<M, ST, W, P, QN, false, false, J>, \
+                                     (const void *)k_render<M, ST, W, P, QN, false, true, J>}
+#define MCPT_KR(M, ST, W, QN, J) {MCPT_KG(M, ST, W, false, QN, J), MCPT_KG(M, ST, W, true, QN, J)}
+#define MCPT_KK(M, QN, J) {{MCPT_KR(M, false, false, QN, J), MCPT_KR(M, false, true, QN, J)}, \
+                           {MCPT_KR(M, true, false, QN, J), MCPT_KR(M, true, true, QN, J)}}
+#define MCPT_KJ(J) {MCPT_KK(MCPT_MODE_EXACT, false, J), MCPT_KK(MCPT_MODE_NOPRUNE, false, J), \
+                    MCPT_KK(MCPT_MODE_EXACT, true, J)}
+  static const void *const kfns[2][3][2][2][2][2] = {MCPT_KJ(false), MCPT_KJ(true)};
+#undef MCPT_KJ
   // the primary-hit pass: [kind][window][pair], no stats
 #define MCPT_KP(M, W, QN) {(const void *)k_render<M, false, W, false, QN, true, false>, \
                            (const void *)k_render<M, false, W, true, QN, true, false>}
@@ -2465,7 +2511,7 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
                              lds_mats + 15) & ~(size_t)15) + pad;
   const size_t lds_win = (((size_t)kWgWaves * kStackWindow * 64 * sizeof(int32_t) + sizeof(LdsUniforms) + lds_top +
                            lds_mats + 15) & ~(size_t)15) + pad;
-  const void *const(*fns)[2][2] = kfns[kind][ctx->stats_on];  // [window][pair][glossy]
+  const void *const(*fns)[2][2] = kfns[p->jitter][kind][ctx->stats_on];  // [window][pair][glossy]
   // stack_window 1 forces the window (tests, experiments) even when the whole stack fits in it, 2 forbids it
   const bool forced = T.stack_window == 1;
   int per_cu_plain = 0, per_cu_win = 0;
@@ -2577,12 +2623,16 @@ static int primary_pass(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rende
 // two or more frames, or for a one-frame call of the same view as the
 // previous call (the reference's one frame per update()); 1 always, 2
 // never.  Speed only: the same bits either way.  *state = mcpt_stats.primary_cache.
+// A jittered call's primary rays differ every frame: it neither reads nor
+// builds the cache whatever the knob says, and leaves a held one (and the
+// record of the previous call's view) as it found them; it still starts its
+// tiles dearest first when the held cache's costs are those of its view.
 static int primary_cache(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_render_params *p,
                          const KernelChoice &K, const mcpt::PlanOut &P, hipStream_t st, RenderArgs &A, int *state) {
   A.prim = nullptr, A.prim_out = nullptr, A.tile_order = nullptr;
   A.prim_cost = nullptr;  // set where the primary-hit pass runs
   *state = 0;
-  if (ctx->tune.primary_cache == 2 || P.tiles <= 0 || p->frames <= 0) return MCPT_OK;
+  if ((ctx->tune.primary_cache == 2 && !p->jitter) || P.tiles <= 0 || p->frames <= 0) return MCPT_OK;
   PrimKey key;
   std::memset(&key, 0, sizeof key);
   key.scene_uid = scene->uid;
@@ -2590,6 +2640,7 @@ static int primary_cache(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_came
   key.w = p->width, key.h = p->height, key.mode = p->mode;
   key.stripe_rows = p->stripe_rows, key.stripe_index = p->stripe_index, key.stripe_count = p->stripe_count;
   const bool have = ctx->prim_valid && std::memcmp(&key, &ctx->prim_key, sizeof key) == 0;
+  if (p->jitter) return have ? tile_order(ctx, P.tiles, false, st, A) : MCPT_OK;
   const bool again = ctx->seen_valid && std::memcmp(&key, &ctx->seen_key, sizeof key) == 0;
   ctx->seen_key = key;
   ctx->seen_valid = true;
@@ -2708,6 +2759,17 @@ int mcpt_generate_rays(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t w, int32_t
   HIP_OK(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_generate, dim3((w + 63) / 64, h), dim3(64), 0, (hipStream_t)stream, *cam, (uint32_t)w,
                      (uint32_t)h, rays);
+  HIP_OK(hipGetLastError());
+  return MCPT_OK;
+}
+
+int mcpt_generate_rays_jittered(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t w, int32_t h, uint32_t *seeds,
+                                mcpt_ray *rays, void *stream) {
+  if (!ctx || !cam || !seeds || !rays || w <= 0 || h <= 0)
+    return mcpt::fail(MCPT_ERR_ARG, "generate_rays_jittered: bad argument");
+  HIP_OK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_generate_jittered, dim3((w + 63) / 64, h), dim3(64), 0, (hipStream_t)stream, *cam, (uint32_t)w,
+                     (uint32_t)h, seeds, rays);
   HIP_OK(hipGetLastError());
   return MCPT_OK;
 }

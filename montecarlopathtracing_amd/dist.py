@@ -62,12 +62,14 @@ def reduce_image(hist, count, seeds, mask, group=None, dst=0):
 
 
 def render_distributed(renderer, scene, camera, width, height, max_depth, max_attempt, frames, seeds,
-                       stripe_rows=16, group=None, mode=0):
+                       stripe_rows=16, group=None, mode=0, jitter=False):
     """Render the whole image across the process group; rank 0 gets the image.
+    `jitter`: Renderer.render_frames' sub-pixel jitter (per-pixel draws, so
+    still the single-GPU image for any GPU count).
     Returns (hist, count, seeds) as numpy on rank 0, None elsewhere."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     st = renderer.new_state(width, height, seeds)
-    kw = dict(stripe_rows=stripe_rows, stripe_index=rank, stripe_count=world, mode=mode)
+    kw = dict(stripe_rows=stripe_rows, stripe_index=rank, stripe_count=world, mode=mode, jitter=jitter)
     if frames >= 4096:  # long runs: each rank times the leaf schedules and S/fetch thresholds on one-block
         # 16-frame calls (same bits; neither block sizing nor tile order is tuned: long calls run
         # max_block_frames blocks, a regime one-block trials do not enter, App.update)

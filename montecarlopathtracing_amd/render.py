@@ -248,10 +248,15 @@ class Renderer:
     # ---------------------------------------------------------- fused path
     def render_frames(self, scene, camera, state, max_depth, max_attempt, frames, frame_begin=None,
                       stripe_rows=16, stripe_index=0, stripe_count=1, mode=L.MODE_EXACT,
-                      frames_per_launch=0, schedule=None):
+                      frames_per_launch=0, schedule=None, jitter=False):
         """Frames [frame_begin, frame_begin+frames) for this GPU's row stripes
         (OpenCL::update x frames + ColorOut accumulation).  `schedule`
-        (L.SCHED_*; default: the scene's, see tune_schedule) only changes speed."""
+        (L.SCHED_*; default: the scene's, see tune_schedule) only changes speed.
+        `jitter` (opt-in antialiasing; mcpt_render_params.jitter): every frame's
+        primary ray goes through a point of the pixel's footprint drawn from
+        the pixel's seed chain instead of its corner; such a call does without
+        the primary-hit cache.  True / False or 0 / 1; another integer is the
+        library's MCPT_ERR_ARG."""
         p = L.RenderParams()
         p.width, p.height = state.width, state.height
         p.max_depth, p.max_attempt = int(max_depth), int(max_attempt)
@@ -261,6 +266,7 @@ class Renderer:
         p.mode = int(mode)
         p.frames_per_launch = int(frames_per_launch)
         p.schedule = int(getattr(scene, "schedule", L.SCHED_PAIRED) if schedule is None else schedule)
+        p.jitter = int(jitter)
         cam = np.ascontiguousarray(camera)
         L.check(L.lib().mcpt_render_frames(self.ctx, scene.handle, L.ptr(cam), ctypes.byref(p), L.ptr(state.seeds),
                                            L.ptr(state.hist), L.ptr(state.count), _stream()))
@@ -272,7 +278,8 @@ class Renderer:
         `frames` frames `trials` times with each schedule on a scratch copy
         of `state` (interleaved, device time of each call), keep the faster
         in scene.schedule.  Both schedules give bit-identical images, so this
-        only moves speed.  Returns (schedule, {schedule: best ms})."""
+        only moves speed.  Keywords (`jitter` among them) go to the scratch
+        renders it times.  Returns (schedule, {schedule: best ms})."""
         sched, _, best = self.tune(scene, camera, state, max_depth, max_attempt, frames, trials, shade_thresholds=None,
                                    fetch_thresholds=None, tile_orders=None, **kw)
         return sched, {k[0]: v for k, v in best.items()}
@@ -297,7 +304,8 @@ class Renderer:
         predict; the minimum favoured lucky runs).  fresh_view: every trial
         call first drops the primary-hit cache, so it pays the primary-hit
         pass and the tile sort as a call of a new view does (bench.py's timed
-        call).  The winner goes to
+        call).  Keywords of render_frames (mode, stripes, `jitter`) go to every
+        scratch render, so a jittered render is tuned as it will run.  The winner goes to
         scene.schedule and the renderer's tuning.  Returns (schedule,
         shade_threshold, {(schedule, shade, fetch, entries, tile_order): median ms})."""
         if getattr(self, "_stats_on", False):
@@ -393,6 +401,18 @@ class Renderer:
         rays = _dev_bytes(width * height * L.RAY.itemsize, self.device)
         cam = np.ascontiguousarray(camera)
         L.check(L.lib().mcpt_generate_rays(self.ctx, L.ptr(cam), width, height, L.ptr(rays), _stream()))
+        return rays
+
+    def generate_rays_jittered(self, camera, width, height, seeds):
+        """generate_rays with a jittered render's sub-pixel offsets
+        (mcpt_generate_rays_jittered): each pixel's two draws come from, and
+        advance, `seeds` (a W*H int32 CUDA tensor, in place)."""
+        if seeds.numel() != width * height or seeds.element_size() != 4 or not seeds.is_cuda:
+            raise L.MCPTError("generate_rays_jittered: seeds must be a CUDA tensor of width*height 32-bit words")
+        rays = _dev_bytes(width * height * L.RAY.itemsize, self.device)
+        cam = np.ascontiguousarray(camera)
+        L.check(L.lib().mcpt_generate_rays_jittered(self.ctx, L.ptr(cam), width, height, L.ptr(seeds), L.ptr(rays),
+                                                    _stream()))
         return rays
 
     def intersect(self, scene, rays, hits=None, tmin=0.001, mode=L.MODE_EXACT):

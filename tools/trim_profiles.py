@@ -28,10 +28,11 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROF = os.path.join(ROOT, "profiles")
 RENDER_KERNELS = re.compile(r"k_render|k_primary|k_tile_")
-# k_render<MODE, STATS, WIN, PAIR, Q-or-node-format, PRIM, G[, VAR]>: PRIM (the
-# primary-hit pass) anchored by position, so a G or VAR argument never reads as it
+# k_render<MODE, STATS, WIN, PAIR, Q-or-node-format, PRIM, G[, VAR or J]>: PRIM (the
+# primary-hit pass) anchored by position, so a G, VAR or J (jittered render)
+# argument never reads as it
 NON_PRIM = re.compile(r"k_render<-?\d+, (?:false|true), (?:false|true), (?:false|true), (?:false|true|\d+), false, "
-                      r"(?:false|true)(?:, \d+)?>")
+                      r"(?:false|true)(?:, (?:\d+|false|true))?>")
 
 
 def _rows(text):
