@@ -258,7 +258,8 @@ typedef struct mcpt_tuning {
  * mcpt_set_pixel_segments' capacity; 4: the rejected T-phase-helper and
  * merged-gather knobs and counters removed from mcpt_tuning / mcpt_stats,
  * `top_levels` added to both; 5: `jitter` appended to mcpt_render_params,
- * mcpt_generate_rays_jittered added).
+ * mcpt_generate_rays_jittered added).  A new struct with a new entry point
+ * changes neither, so mcpt_denoise_params and mcpt_denoise came in at 5.
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
 #define MCPT_ABI_VERSION 5
@@ -418,6 +419,46 @@ int mcpt_accumulate(mcpt_ctx *ctx, float *color_dev, float *hist_dev, int32_t *c
  * shows the current frame's colours before MAX_ATTEMPT and frameBuffer (the
  * running mean, mcpt_state's hist) after.  n = pixels; may run in place.    */
 int mcpt_gamma_preview(mcpt_ctx *ctx, const float *color_dev, float *out_dev, int64_t n, void *stream);
+
+/* Opt-in denoise post-pass (no reference counterpart): a
+ * count-aware, geometry-guided a-trous filter of the accumulated image.  The
+ * history keeps the mean over a pixel's NON-ZERO samples, so a short render
+ * is mostly count-0 pixels; every tap is weighted by its count, so such a
+ * pixel carries no information instead of carrying black.
+ *  hits_dev   width*height first hits of the view, mcpt_generate_rays then
+ *             mcpt_intersect in the caller's render mode (the corner ray's,
+ *             also for a jittered render);
+ *  hist_dev, count_dev   the image state, read only;
+ *  out_dev    width*height float4, never hist_dev.
+ * A pixel is filtered when its first hit is a hit (t < FLT_MAX) with
+ * material_id < n_mats on a MCPT_DIFFUSE or MCPT_GLOSSY material; every other
+ * pixel comes out as hist_dev's float4 bit for bit and is never a tap.  A
+ * filtered pixel p starts from c = hist.xyz, W = (float)count and takes, for
+ * i = 0 .. iterations-1 with s = 2^i, over the 5x5 taps q = p + s*(dx, dy)
+ * that lie inside the image, are filtered, have W_q > 0 and p's material id,
+ *   w_q = k[dx] k[dy] W_q exp(-|n_p - n_q|^2 / sigma_normal^2
+ *                             - (n_p . (x_q - x_p))^2 / (sigma_plane D)^2
+ *                             - |c_p - c_q|^2 / (sigma_color 2^-i)^2),
+ * k = (1, 4, 6, 4, 1) / 16, D = the length of the scene root box's diagonal,
+ * the colour term only with sigma_color > 0 and W_p > 0; then c = sum(w_q c_q)
+ * / sum(w_q), W = sum(w_q), or, when no tap counts, c unchanged and W = 0.
+ * It comes out as (c, 0).  iterations = 0 copies hist_dev.  The call writes
+ * out_dev and context-owned scratch (64 B per pixel, grown on demand) and
+ * nothing else: not hist, count or seeds, nor any cache of the context, so a
+ * render continued afterwards is unaffected.  Stream-ordered and asynchronous.
+ * MCPT_ERR_ARG: a null pointer, a non-positive size, iterations outside 0..8,
+ * a sigma that is not finite, sigma_normal or sigma_plane <= 0, sigma_color
+ * < 0, out_dev == hist_dev, hits_dev / hist_dev / out_dev not 16-B aligned.  */
+typedef struct mcpt_denoise_params {
+  int32_t iterations;      /* 0..8; 0 copies hist                        */
+  float sigma_normal;      /* > 0                                          */
+  float sigma_plane;       /* > 0, as a fraction of the scene diagonal     */
+  float sigma_color;       /* >= 0; 0: no colour term                      */
+} mcpt_denoise_params;
+int mcpt_denoise(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_hit *hits_dev,
+                 const float *hist_dev, const int32_t *count_dev,
+                 int32_t width, int32_t height,
+                 const mcpt_denoise_params *params, float *out_dev, void *stream);
 
 /* Counters of the last render call (segments etc. need stats enabled);
  * waits for that call's work to finish.                                   */

@@ -1,7 +1,7 @@
 """Command line: render a reference config.json on the GPU(s) and write the .hdr,
 or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
-    python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter]
+    python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -19,6 +19,9 @@ def parser():
     ap.add_argument("--preview", default=None, help="also write the gamma-2.2 display image (testkernel.cl) as PNG")
     ap.add_argument("--jitter", action="store_true",
                     help="sub-pixel jitter (antialiasing) even if the config entry has no \"jitter\": true")
+    ap.add_argument("--denoise", action="store_true",
+                    help="also write <objname>_denoised.hdr, the count-aware geometry-guided denoise of the image "
+                         "(with --preview the PNG shows it), even if the config entry has no \"denoise\": true")
     return ap
 
 
@@ -34,7 +37,8 @@ def main(argv=None):
     if ws > 1:
         return _main_dist(a)
     from .app import App
-    app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None)
+    app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
+              denoise=True if a.denoise else None)
     t0 = time.time()
     if a.frames:
         app.update(a.frames)
@@ -85,6 +89,16 @@ def _main_dist(a):
         path = os.path.join(a.out, cfg.GETOBJNAME() + ".hdr")
         S.write_hdr(path, out[0].reshape(h, w, 4), flip=True)
         print("wrote", path)
+        if a.denoise or cfg.DENOISE():
+            # the same filter on the reduced image: the whole image's first hits are one extra pass here
+            from .app import App
+            st = rnd.new_state(w, h, out[2])
+            st.hist.copy_(torch.from_numpy(out[0]).view(-1, 4))
+            st.count.copy_(torch.from_numpy(out[1]))
+            hits = rnd.first_hits(sc, S.parse_camera(cfg.GETCAMERA()), w, h)
+            den = rnd.denoise(sc, hits, st).cpu().numpy().reshape(h, w, 4)
+            S.write_hdr(App.denoised_path(path), den, flip=True)
+            print("wrote", App.denoised_path(path))
     dist.destroy_process_group()
     return 0
 

@@ -62,6 +62,12 @@ class Tuning(ctypes.Structure):
         "top_levels")]
 
 
+class DenoiseParams(ctypes.Structure):
+    """mcpt_denoise_params (16 B)."""
+    _fields_ = [("iterations", ctypes.c_int32), ("sigma_normal", ctypes.c_float),
+                ("sigma_plane", ctypes.c_float), ("sigma_color", ctypes.c_float)]
+
+
 class MCPTError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -100,6 +106,7 @@ SIGNATURES = {
     "mcpt_shade": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "mcpt_accumulate": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),
     "mcpt_gamma_preview": (_I32, [_P, _P, _P, _I64, _P]),
+    "mcpt_denoise": (_I32, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "mcpt_set_tuning": (_I32, [_P, _P]),
     "mcpt_get_tuning": (_I32, [_P, _P]),
     "mcpt_drop_caches": (_I32, [_P]),

@@ -12,6 +12,13 @@ Extension: a config entry with "jitter": true (or App(..., jitter=True), the
 command line's --jitter) renders with sub-pixel jitter, every frame's primary
 ray through a drawn point of its pixel's footprint (antialiasing); the
 reference has none, and the default keeps its corner ray bit for bit.
+
+Extension: "denoise": true (App(..., denoise=True), --denoise) also writes
+<objname>_denoised.hdr, the accumulated image through Renderer.denoise with
+its defaults.  <objname>.hdr keeps its bytes, and the render state is not
+touched.  The filter's guide is the first hit of each pixel's corner ray,
+also when the render is jittered: the geometry a jittered pixel averages over
+is within one pixel of it.
 """
 import os
 
@@ -46,7 +53,7 @@ def config_scene(cfg, root, device=0, material_override=None):
 
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
-                 material_override=None, jitter=None):
+                 material_override=None, jitter=None, denoise=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -60,6 +67,7 @@ class App:
         if material_override is None and self.cfg.entry.get("materials") == "diffuse_only":
             self.material_override = S.diffuse_only
         self.jitter = self.cfg.JITTER() if jitter is None else bool(jitter)  # None: the entry's "jitter" key
+        self.denoise = self.cfg.DENOISE() if denoise is None else bool(denoise)  # None: the entry's "denoise" key
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -108,10 +116,28 @@ class App:
         return self.state
 
     def output_picture(self, path=None):
-        """ThirdPartyWrapper::outputPicture(<objname>.hdr, frameBuffer)."""
+        """ThirdPartyWrapper::outputPicture(<objname>.hdr, frameBuffer); with
+        denoise on also <objname>_denoised.hdr beside it (denoised_path)."""
         path = path or os.path.join(self.out_dir, self.cfg.GETOBJNAME() + ".hdr")
         S.write_hdr(path, self.state.image(), flip=True)
+        if self.denoise:
+            S.write_hdr(self.denoised_path(path), self.denoised(), flip=True)
         return path
+
+    @staticmethod
+    def denoised_path(path):
+        """<name>.hdr -> <name>_denoised.hdr."""
+        return (path[:-4] if path.endswith(".hdr") else path) + "_denoised.hdr"
+
+    def denoised(self):
+        """The accumulated image through Renderer.denoise (its defaults), H x W
+        x 4 floats (w = 0 on filtered pixels), guided by the corner rays' first
+        hits; the state is only read."""
+        if not self._init:
+            self.init()
+        hits = self.renderer.first_hits(self.scene, self.camera, self.w, self.h)
+        out = self.renderer.denoise(self.scene, hits, self.state)
+        return out.cpu().numpy().reshape(self.h, self.w, 4)
 
     def run(self):
         self.update(self.cfg.MAXATTEPMT() + 1)
@@ -123,8 +149,13 @@ class App:
     def preview(self):
         """ColorOut's display pass (testkernel.cl func, colorout.cpp:69-70 once
         the history is complete): the running mean gamma-2.2 encoded, H x W x 4
-        floats (w = 0), as the reference writes to its RGBA32F texture."""
+        floats (w = 0), as the reference writes to its RGBA32F texture.  With
+        denoise on it encodes the denoised image."""
         if not self._init:
             self.init()
-        out = self.renderer.gamma_preview(self.state.hist)
+        src = self.state.hist
+        if self.denoise:
+            hits = self.renderer.first_hits(self.scene, self.camera, self.w, self.h)
+            src = self.renderer.denoise(self.scene, hits, self.state)
+        out = self.renderer.gamma_preview(src)
         return out.cpu().numpy().reshape(self.h, self.w, 4)

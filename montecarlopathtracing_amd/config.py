@@ -57,6 +57,10 @@ class Config:
         self.jitter = c.get("jitter", False)
         if not isinstance(self.jitter, bool):
             raise ValueError('config "jitter" must be true or false, got %r' % (self.jitter,))
+        # "denoise": true also writes the denoised image (Renderer.denoise)
+        self.denoise = c.get("denoise", False)
+        if not isinstance(self.denoise, bool):
+            raise ValueError('config "denoise" must be true or false, got %r' % (self.denoise,))
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -98,3 +102,4 @@ class Config:
     def USEOPENCL(self): return self.opencl
     def GETOBJS(self): return self.objs
     def JITTER(self): return self.jitter  # extension: sub-pixel jitter of the render path
+    def DENOISE(self): return self.denoise  # extension: the denoise post-pass

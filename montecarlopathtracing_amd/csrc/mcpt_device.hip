@@ -38,6 +38,7 @@
 #include "mcpt_plan.h"  // the launch plan and its constants (kHandoffWords, kHandoffMaxBytes, ...)
 #include "mcpt_queue.h"  // queue entries, block frames, the hand-off record, the wave's queue state
 #include "mcpt_upload.h"
+#include "mcpt_denoise.h"  // the two accessors mcpt_denoise.hip reaches the handles through
 
 using namespace mcpt;
 
@@ -275,6 +276,8 @@ struct mcpt_ctx {
   uint32_t *d_entry_log = nullptr;        // MCPT_PHASE_TIMING: 3 words per (pixel, block) of the last launch
   int64_t entry_log_cap = 0, entry_log_n = 0;
   int32_t entry_log_blocks = 0;
+  void *d_denoise = nullptr;              // mcpt_denoise's planes (mcpt_denoise.h), grown on demand
+  int64_t denoise_cap = 0;                // pixels
 };
 
 struct mcpt_state {
@@ -1719,7 +1722,8 @@ int mcpt_ctx_destroy(mcpt_ctx *c) {
   if (c->d_stats) (void)hipFree(c->d_stats);
   if (c->last_pending && c->ev1) (void)hipEventSynchronize(c->ev1);  // the last render may still use the buffers
   for (void *p : {(void *)c->d_queue, (void *)c->d_handoff, (void *)c->d_spill, (void *)c->d_prim, (void *)c->d_prim_cost,
-                  (void *)c->d_tile_order, (void *)c->d_tile_key, (void *)c->d_wave_log, (void *)c->d_entry_log})
+                  (void *)c->d_tile_order, (void *)c->d_tile_key, (void *)c->d_wave_log, (void *)c->d_entry_log,
+                  c->d_denoise})
     if (p) (void)hipFree(p);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2445,6 +2449,25 @@ static int grow_dev(int64_t &cap, int64_t need, void **a, size_t a_bytes, void *
   cap = need;
   return MCPT_OK;
 }
+
+// mcpt_denoise.hip reaches the handles through these two (mcpt_denoise.h)
+extern "C++" {
+namespace mcpt {
+int denoise_scene(const mcpt_scene *scene, DenoiseScene *out) {
+  out->device = scene->device;
+  out->mats = scene->mats, out->n_mats = scene->n_mats;
+  const f4 lo = scene->view.root_min, hi = scene->view.root_max;
+  out->root_min[0] = lo.x, out->root_min[1] = lo.y, out->root_min[2] = lo.z;
+  out->root_max[0] = hi.x, out->root_max[1] = hi.y, out->root_max[2] = hi.z;
+  return MCPT_OK;
+}
+int denoise_scratch(mcpt_ctx *ctx, int64_t n_px, void **scratch, int *device) {
+  MCPT_TRY(grow_dev(ctx->denoise_cap, n_px, &ctx->d_denoise, (size_t)kDenoiseBytesPerPixel));
+  *scratch = ctx->d_denoise, *device = ctx->device;
+  return MCPT_OK;
+}
+}  // namespace mcpt
+}  // extern "C++"
 
 // The k_render instantiation of a render call and what it runs with.
 struct KernelChoice {
