@@ -259,7 +259,9 @@ typedef struct mcpt_tuning {
  * merged-gather knobs and counters removed from mcpt_tuning / mcpt_stats,
  * `top_levels` added to both; 5: `jitter` appended to mcpt_render_params,
  * mcpt_generate_rays_jittered added).  A new struct with a new entry point
- * changes neither, so mcpt_denoise_params and mcpt_denoise came in at 5.
+ * changes neither, so mcpt_denoise_params and mcpt_denoise came in at 5, and
+ * so did mcpt_environment with mcpt_scene_set_environment, mcpt_env_eval and
+ * mcpt_decode_hdr.
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
 #define MCPT_ABI_VERSION 5
@@ -312,6 +314,20 @@ int mcpt_write_hdr(const char *path, int32_t width, int32_t height,
  * MCPT_ERR_ARG if `cap` is too small for it.                              */
 int64_t mcpt_encode_hdr(int32_t width, int32_t height, const float *rgba,
                         int32_t flip_vertically, uint8_t *out, int64_t cap);
+/* Radiance RGBE reader (the format mcpt_write_hdr writes; an environment map
+ * for mcpt_scene_set_environment): `len` bytes of a file with the
+ * "#?RADIANCE" (or "#?RGBE") magic, a FORMAT=32-bit_rle_rgbe line and the
+ * "-Y h +X w" resolution line, run-length encoded or flat scanlines.  A
+ * texel decodes as stb_image does, m * 2^(e - 136) per channel and 0 when
+ * e == 0.  *width and *height are set once the header is read (rgb_out NULL:
+ * the size query); then width * height * 3 floats go to rgb_out, rows in file
+ * order (the first row of the file first), `cap` its capacity in floats
+ * (MCPT_ERR_ARG when too small).  A parser of files from outside: a truncated
+ * file, a run longer than its scanline, a scanline width that disagrees with
+ * the header, a bad header or width * height > 2^26 is MCPT_ERR_PARSE, and no
+ * input makes it read past `len` or write past the image.                  */
+int mcpt_decode_hdr(const uint8_t *bytes, int64_t len, int32_t *width, int32_t *height,
+                    float *rgb_out, int64_t cap);
 
 /* ---------------------------------------------------------- device side */
 
@@ -459,6 +475,55 @@ int mcpt_denoise(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_hit *hits_de
                  const float *hist_dev, const int32_t *count_dev,
                  int32_t width, int32_t height,
                  const mcpt_denoise_params *params, float *out_dev, void *stream);
+
+/* Opt-in environment lighting (no reference counterpart): what
+ * a ray that leaves the scene picks up.  The reference, and a scene without
+ * an environment, give such a ray black (shade.cl:89-93).
+ * An environment is a scale (r, g, b: finite, >= 0; scale[3] is ignored), an
+ * optional lat-long map and a rotation rotate_deg (finite, degrees about +Y).
+ * The map is width x height RGB float texels, 3 floats each, rows in file
+ * order with row 0 the top (+Y), every texel finite and >= 0, 1 <= width,
+ * height and width * height <= 2^26; map_rgb NULL: no map, width and height
+ * ignored.  For a unit ray direction d, in real arithmetic (the kernels
+ * evaluate it in fp32, tests/env_ref.py restates it in float64):
+ *   d' = (c d.x + s d.z, d.y, -s d.x + c d.z), c = cos(rotate), s = sin(rotate)
+ *        computed in double on the host and rounded to float once;
+ *   u = 0.5 + atan2(d'.x, -d'.z) / (2 pi),  v = acos(clamp(d'.y, -1, 1)) / pi;
+ *   x = u * width - 0.5,  y = v * height - 0.5,  i0 = floor(x),  j0 = floor(y),
+ *   fx = x - i0, fy = y - j0;  T = the bilinear mix of texels (i0, j0),
+ *   (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1) with weights (1 - fx)(1 - fy),
+ *   fx (1 - fy), (1 - fx) fy, fx fy, columns taken modulo width, rows clamped
+ *   to [0, height - 1];
+ *   L = (scale.r T.r, scale.g T.g, scale.b T.b, 0).
+ * Without a map L = (scale.r, scale.g, scale.b, 0) and no trigonometry runs.
+ * A path whose segment misses ends as it does without an environment, but its
+ * colour is color * L instead of 0, in mcpt_render_frames and in mcpt_shade.
+ * L.w = 0 on purpose: a zero-radiance environment gives the all-zero sample
+ * the history skips, so scale = 0 renders the bits of no environment.  The
+ * depth cap, the history rule, max_attempt, the seed chain (the lookup draws
+ * nothing), the hand-off and the primary-hit records are untouched.
+ * mcpt_scene_set_environment copies and uploads the map (float4 texels in
+ * HBM), replacing a previous environment of the scene; env NULL clears it (the
+ * bits of a scene that never had one).  mcpt_scene_destroy frees the map.  The
+ * context's primary-hit cache stays valid: it holds hits, not radiance.  It
+ * waits for work already enqueued on the scene's GPU before it frees a
+ * previous map.  MCPT_ERR_ARG (the environment unchanged): a null context or
+ * scene, a scale or rotate_deg that is not finite, a negative scale, a map
+ * with a dimension < 1, more than 2^26 texels, or a texel that is negative
+ * or not finite.                                                          */
+typedef struct mcpt_environment {
+  float scale[4];
+  const float *map_rgb;             /* host, width * height * 3 floats, or NULL */
+  int32_t width, height;
+  float rotate_deg;
+} mcpt_environment;
+int mcpt_scene_set_environment(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_environment *env);
+/* L of the scene's environment for n rays (their direction's xyz, taken as
+ * unit vectors) into out_rgba_dev, n float4; zeros when the scene has no
+ * environment.  Both arrays on the device, 16-B aligned.  Stream-ordered and
+ * asynchronous.  With mcpt_generate_rays: the view's background plate.     */
+int mcpt_env_eval(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays_dev, int64_t n,
+                  float *out_rgba_dev, void *stream);
 
 /* Counters of the last render call (segments etc. need stats enabled);
  * waits for that call's work to finish.                                   */

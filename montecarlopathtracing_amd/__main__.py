@@ -2,6 +2,7 @@
 or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
+        [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -22,7 +23,55 @@ def parser():
     ap.add_argument("--denoise", action="store_true",
                     help="also write <objname>_denoised.hdr, the count-aware geometry-guided denoise of the image "
                          "(with --preview the PNG shows it), even if the config entry has no \"denoise\": true")
+    ap.add_argument("--env", default=None, metavar="R,G,B",
+                    help="constant environment: rays that leave the scene pick up this radiance instead of black "
+                         "(overrides the config entry's \"environment\")")
+    ap.add_argument("--env-map", default=None, metavar="FILE",
+                    help="lat-long .hdr environment map (row 0 the top; a path relative to the working directory; "
+                         "overrides the config entry's \"environment\")")
+    ap.add_argument("--env-scale", default=None, metavar="S|R,G,B",
+                    help="factor on the map (--env-map, or the config entry's map)")
+    ap.add_argument("--env-rotate", type=float, default=None, metavar="DEG",
+                    help="rotation of the map about +Y in degrees (--env-map, or the config entry's map)")
     return ap
+
+
+def _numbers(text, what, counts):
+    try:
+        v = [float(x) for x in text.split(",")]
+    except ValueError:
+        v = []
+    if len(v) not in counts:
+        raise ValueError("%s: expected %s comma-separated numbers, got %r" % (what, " or ".join(map(str, counts)), text))
+    return v
+
+
+def cli_environment(a, cfg):
+    """The command line's environment in the config key's form, or None: the
+    entry's own.  --env and --env-map replace the entry's; --env-scale and
+    --env-rotate alone adjust the entry's map."""
+    if a.env is not None and a.env_map is not None:
+        raise ValueError("--env and --env-map exclude each other")
+    adjust = a.env_scale is not None or a.env_rotate is not None
+    if a.env is not None:
+        if adjust:
+            raise ValueError("--env-scale and --env-rotate belong to a map, not to --env")
+        return {"color": _numbers(a.env, "--env", (3,))}
+    own = cfg.ENVIRONMENT()
+    if a.env_map is not None:
+        e = {"map": os.path.abspath(a.env_map)}
+    elif not adjust:
+        return None
+    elif own is not None and own["map"] is not None:
+        e = {"map": own["map"], "scale": list(own["scale"]), "rotate": own["rotate"]}
+    else:
+        raise ValueError("--env-scale and --env-rotate need --env-map or a config entry with an environment map")
+    if a.env_scale is not None:
+        v = _numbers(a.env_scale, "--env-scale", (1, 3))
+        e["scale"] = v[0] if len(v) == 1 else v
+    if a.env_rotate is not None:
+        e["rotate"] = a.env_rotate
+    return e
 
 
 def main(argv=None):
@@ -38,7 +87,7 @@ def main(argv=None):
         return _main_dist(a)
     from .app import App
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
-              denoise=True if a.denoise else None)
+              denoise=True if a.denoise else None, environment=cli_environment(a, cfg))
     t0 = time.time()
     if a.frames:
         app.update(a.frames)
@@ -60,7 +109,7 @@ def _main_dist(a):
     from . import dist as D
     from . import render as R
     from . import scene as S
-    from .app import config_scene
+    from .app import apply_environment, config_scene
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # MCPT_DIST_SHARED_GPU=1 rehearses the N-rank job on a one-GPU box: every
     # rank on device 0, gloo for the one reduce (tests/test_gpu_dist.py)
@@ -81,6 +130,9 @@ def _main_dist(a):
     data = config_scene(cfg, root, local)
     rnd = R.Renderer(local)
     sc = rnd.upload(data)
+    # every rank lights its own scene: its stripes' misses read the same environment
+    env = cli_environment(a, cfg)
+    apply_environment(rnd, sc, cfg.ENVIRONMENT() if env is None else C.parse_environment(env), cfg, root)
     w, h = cfg.WIDTH(), cfg.HEIGHT()
     frames = a.frames or cfg.MAXATTEPMT() + 1
     out = D.render_distributed(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, cfg.MAXDEPTH(), cfg.MAXATTEPMT(),

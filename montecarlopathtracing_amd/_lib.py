@@ -68,6 +68,13 @@ class DenoiseParams(ctypes.Structure):
                 ("sigma_plane", ctypes.c_float), ("sigma_color", ctypes.c_float)]
 
 
+class Environment(ctypes.Structure):
+    """mcpt_environment: scale[4], map_rgb (host float32 RGB rows, or NULL),
+    width, height, rotate_deg."""
+    _fields_ = [("scale", ctypes.c_float * 4), ("map_rgb", ctypes.c_void_p),
+                ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("rotate_deg", ctypes.c_float)]
+
+
 class MCPTError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -92,6 +99,9 @@ SIGNATURES = {
     "mcpt_bvh_stack_depth": (_I32, [_P, _I64, _P]),
     "mcpt_write_hdr": (_I32, [_S, _I32, _I32, _P, _I32]),
     "mcpt_encode_hdr": (_I64, [_I32, _I32, _P, _I32, _P, _I64]),
+    "mcpt_decode_hdr": (_I32, [_P, _I64, _P, _P, _P, _I64]),
+    "mcpt_scene_set_environment": (_I32, [_P, _P, _P]),
+    "mcpt_env_eval": (_I32, [_P, _P, _P, _I64, _P, _P]),
     "mcpt_ctx_create": (_I32, [_I32, _P]),
     "mcpt_ctx_destroy": (_I32, [_P]),
     "mcpt_device_count": (_I32, [_P]),

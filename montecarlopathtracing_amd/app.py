@@ -19,6 +19,13 @@ its defaults.  <objname>.hdr keeps its bytes, and the render state is not
 touched.  The filter's guide is the first hit of each pixel's corner ray,
 also when the render is jittered: the geometry a jittered pixel averages over
 is within one pixel of it.
+
+Extension: "environment": {"color": [r, g, b]} or {"map": "sky.hdr", "scale":
+s | [r, g, b], "rotate": deg} (App(..., environment={...}), --env / --env-map)
+lights the rays that leave the scene with a constant or a lat-long .hdr map
+instead of the reference's black (Renderer.set_environment).  The denoise
+pass needs nothing for it: a pixel whose first hit is a miss passes through,
+so the sky stays sharp.
 """
 import os
 
@@ -51,9 +58,22 @@ def config_scene(cfg, root, device=0, material_override=None):
     return data.with_nodes(R.treelet_gpu_device(data.nodes, device))
 
 
+def apply_environment(renderer, scene, env, cfg, root):
+    """Set a config entry's environment (config.parse_environment's dict, or
+    None: leave the reference's black) on an uploaded scene; a map's path is
+    relative to the entry's directory.  App.init and every rank of the
+    multi-GPU CLI go through this."""
+    if env is None:
+        return
+    texels = None
+    if env["map"] is not None:
+        texels = S.read_hdr(os.path.join(root, cfg.GETDIRECTORY(), env["map"]))
+    renderer.set_environment(scene, scale=env["scale"], map=texels, rotate=env["rotate"])
+
+
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
-                 material_override=None, jitter=None, denoise=None):
+                 material_override=None, jitter=None, denoise=None, environment=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -68,6 +88,8 @@ class App:
             self.material_override = S.diffuse_only
         self.jitter = self.cfg.JITTER() if jitter is None else bool(jitter)  # None: the entry's "jitter" key
         self.denoise = self.cfg.DENOISE() if denoise is None else bool(denoise)  # None: the entry's "denoise" key
+        # None: the entry's "environment" key; else that key's value ({"color": ..} or {"map": ..})
+        self.environment = self.cfg.ENVIRONMENT() if environment is None else C.parse_environment(environment)
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -86,6 +108,7 @@ class App:
         self.camera = S.parse_camera(cam)
         self.renderer = R.Renderer(self.device)
         self.scene = self.renderer.upload(self.data)
+        apply_environment(self.renderer, self.scene, self.environment, self.cfg, self.root)
         self.state = self.renderer.new_state(self.w, self.h, self.seeds)
         self._init = True
 

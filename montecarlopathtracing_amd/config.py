@@ -7,6 +7,7 @@ whitespace (MCPT/json.hpp:3037-3043); ``configid`` selects one entry of the
 (MCPT/config.cpp:128-145, MCPT/config.h:8-30) with the same defaults.
 """
 import json
+import math
 
 
 def strip_hash_comments(text):
@@ -38,6 +39,53 @@ def loads(text):
     return json.loads(strip_hash_comments(text))
 
 
+def _env_number(v, what):
+    """A finite JSON number (bool is not one)."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+        raise ValueError('config "environment": %s must be a finite number, got %r' % (what, v))
+    return float(v)
+
+
+def _env_rgb(v, what):
+    if not isinstance(v, (list, tuple)) or len(v) != 3:
+        raise ValueError('config "environment": %s must be [r, g, b], got %r' % (what, v))
+    rgb = tuple(_env_number(x, what) for x in v)
+    if min(rgb) < 0:
+        raise ValueError('config "environment": %s must be >= 0, got %r' % (what, v))
+    return rgb
+
+
+def parse_environment(e):
+    """The "environment" extension key of a config entry ->
+    {"scale": (r, g, b), "map": path or None, "rotate": degrees}.
+    Form one: {"color": [r, g, b]}, a constant environment.  Form two:
+    {"map": "sky.hdr", "scale": s | [r, g, b], "rotate": deg}, a lat-long .hdr
+    relative to the entry's "directory" ("scale" defaults to 1, "rotate" to 0).
+    ValueError on wrong types, negative or non-finite values, unknown sub-keys
+    or a mix of the two forms."""
+    if not isinstance(e, dict):
+        raise ValueError('config "environment" must be an object, got %r' % (e,))
+    if "color" in e:
+        if set(e) != {"color"}:
+            raise ValueError('config "environment": "color" stands alone, got keys %r' % (sorted(e),))
+        return {"scale": _env_rgb(e["color"], '"color"'), "map": None, "rotate": 0.0}
+    if "map" not in e:
+        raise ValueError('config "environment" needs "color" or "map", got keys %r' % (sorted(e),))
+    unknown = set(e) - {"map", "scale", "rotate"}
+    if unknown:
+        raise ValueError('config "environment": unknown keys %r' % (sorted(unknown),))
+    if not isinstance(e["map"], str) or not e["map"]:
+        raise ValueError('config "environment": "map" must be a file name, got %r' % (e["map"],))
+    s = e.get("scale", 1.0)
+    if isinstance(s, (list, tuple)):
+        scale = _env_rgb(s, '"scale"')
+    else:
+        scale = (_env_number(s, '"scale"'),) * 3
+        if scale[0] < 0:
+            raise ValueError('config "environment": "scale" must be >= 0, got %r' % (s,))
+    return {"scale": scale, "map": e["map"], "rotate": _env_number(e.get("rotate", 0.0), '"rotate"')}
+
+
 class Config:
     """One selected entry of a reference config.json (config.cpp:72-122)."""
 
@@ -61,6 +109,9 @@ class Config:
         self.denoise = c.get("denoise", False)
         if not isinstance(self.denoise, bool):
             raise ValueError('config "denoise" must be true or false, got %r' % (self.denoise,))
+        # "environment": what a ray that leaves the scene picks up
+        # (Renderer.set_environment); None: the reference's black
+        self.environment = parse_environment(c["environment"]) if "environment" in c else None
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -103,3 +154,4 @@ class Config:
     def GETOBJS(self): return self.objs
     def JITTER(self): return self.jitter  # extension: sub-pixel jitter of the render path
     def DENOISE(self): return self.denoise  # extension: the denoise post-pass
+    def ENVIRONMENT(self): return self.environment  # extension: parse_environment's dict, or None

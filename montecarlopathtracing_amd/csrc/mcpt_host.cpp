@@ -670,6 +670,141 @@ extern "C" int64_t mcpt_encode_hdr(int32_t width, int32_t height, const float *r
   return n;
 }
 
+// Radiance RGBE reader, the inverse of the encoder above for the files it and
+// stb_image_write produce, decoding as stb_image.h does (stbi__hdr_load,
+// stbi__hdr_convert).  A parser of files from outside: every read is checked
+// against `len` and every write against the scanline.
+namespace {
+
+struct Source {
+  const uint8_t *p;
+  int64_t len, at;
+  bool get(uint8_t *b) {
+    if (at >= len) return false;
+    *b = p[at++];
+    return true;
+  }
+  // one header line without its '\n'; false at the end of the input
+  bool line(std::string *out) {
+    out->clear();
+    if (at >= len) return false;
+    while (at < len && p[at] != '\n') {
+      if (out->size() >= 1024) return false;
+      out->push_back((char)p[at++]);
+    }
+    if (at >= len) return false;  // a header line ends with its newline
+    ++at;
+    return true;
+  }
+};
+
+inline void rgbe_to_float(float *out, const uint8_t *in) {  // stb_image.h stbi__hdr_convert
+  if (in[3] != 0) {
+    const float f1 = std::ldexp(1.0f, (int)in[3] - (128 + 8));
+    out[0] = in[0] * f1, out[1] = in[1] * f1, out[2] = in[2] * f1;
+  } else {
+    out[0] = out[1] = out[2] = 0.0f;
+  }
+}
+
+// "-Y h +X w": positive decimal numbers, nothing else on the line
+bool parse_resolution(const std::string &s, int64_t *w, int64_t *h) {
+  size_t i = 0;
+  auto number = [&](int64_t *v) {
+    if (i >= s.size() || s[i] < '0' || s[i] > '9') return false;
+    int64_t x = 0;
+    while (i < s.size() && s[i] >= '0' && s[i] <= '9') {
+      x = x * 10 + (s[i++] - '0');
+      if (x > (int64_t)1 << 32) return false;
+    }
+    *v = x;
+    return true;
+  };
+  if (s.compare(0, 3, "-Y ") != 0) return false;
+  i = 3;
+  if (!number(h)) return false;
+  while (i < s.size() && s[i] == ' ') ++i;
+  if (s.compare(i, 3, "+X ") != 0) return false;
+  i += 3;
+  if (!number(w)) return false;
+  return i == s.size();
+}
+
+}  // namespace
+
+extern "C" int mcpt_decode_hdr(const uint8_t *bytes, int64_t len, int32_t *width, int32_t *height, float *rgb_out,
+                               int64_t cap) {
+  if (!bytes || len < 0 || !width || !height) return fail(MCPT_ERR_ARG, "decode_hdr: bad argument");
+  Source s{bytes, len, 0};
+  std::string tok;
+  if (!s.line(&tok) || (tok != "#?RADIANCE" && tok != "#?RGBE")) return fail(MCPT_ERR_PARSE, "decode_hdr: not a Radiance file");
+  bool format = false;
+  for (;;) {
+    if (!s.line(&tok)) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated header");
+    if (tok.empty()) break;
+    if (tok == "FORMAT=32-bit_rle_rgbe") format = true;
+  }
+  if (!format) return fail(MCPT_ERR_PARSE, "decode_hdr: not the 32-bit_rle_rgbe format");
+  int64_t w = 0, h = 0;
+  if (!s.line(&tok) || !parse_resolution(tok, &w, &h)) return fail(MCPT_ERR_PARSE, "decode_hdr: bad resolution line");
+  if (w < 1 || h < 1 || w > INT32_MAX || h > INT32_MAX || w * h > ((int64_t)1 << 26))
+    return fail(MCPT_ERR_PARSE, "decode_hdr: dimensions out of range (width * height <= 2^26)");
+  *width = (int32_t)w, *height = (int32_t)h;
+  if (!rgb_out) return MCPT_OK;  // the size query
+  if (cap < w * h * 3) return fail(MCPT_ERR_ARG, "decode_hdr: output buffer too small");
+  uint8_t px[4];
+  auto pixel = [&](uint8_t *o) { return s.get(o) && s.get(o + 1) && s.get(o + 2) && s.get(o + 3); };
+  auto flat = [&](int64_t first) {  // flat RGBE pixels from pixel index `first` on
+    for (int64_t k = first; k < w * h; ++k) {
+      if (!pixel(px)) return false;
+      rgbe_to_float(rgb_out + 3 * k, px);
+    }
+    return true;
+  };
+  if (w < 8 || w >= 32768) {
+    if (!flat(0)) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated pixel data");
+    return MCPT_OK;
+  }
+  std::vector<uint8_t> scan((size_t)w * 4);
+  for (int64_t j = 0; j < h; ++j) {
+    if (!pixel(px)) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated scanline");
+    if (px[0] != 2 || px[1] != 2 || (px[2] & 0x80)) {
+      // not run-length encoded: a flat file whose first pixel this is (stb
+      // takes that turn at any scanline; only the first can be meant)
+      if (j != 0) return fail(MCPT_ERR_PARSE, "decode_hdr: bad scanline header");
+      rgbe_to_float(rgb_out, px);
+      if (!flat(1)) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated pixel data");
+      return MCPT_OK;
+    }
+    if ((((int64_t)px[2] << 8) | px[3]) != w) return fail(MCPT_ERR_PARSE, "decode_hdr: scanline width disagrees with the header");
+    for (int c = 0; c < 4; ++c) {
+      uint8_t *comp = scan.data() + (size_t)w * c;
+      int64_t i = 0;
+      while (i < w) {
+        uint8_t count, value;
+        if (!s.get(&count)) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated scanline");
+        const bool run = count > 128;
+        int64_t n = run ? count - 128 : count;
+        if (n == 0 || n > w - i) return fail(MCPT_ERR_PARSE, "decode_hdr: run longer than the scanline");
+        if (run) {
+          if (!s.get(&value)) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated scanline");
+          std::memset(comp + i, value, (size_t)n);
+        } else {
+          if (s.len - s.at < n) return fail(MCPT_ERR_PARSE, "decode_hdr: truncated scanline");
+          std::memcpy(comp + i, s.p + s.at, (size_t)n);
+          s.at += n;
+        }
+        i += n;
+      }
+    }
+    for (int64_t i = 0; i < w; ++i) {
+      const uint8_t q[4] = {scan[(size_t)i], scan[(size_t)(w + i)], scan[(size_t)(2 * w + i)], scan[(size_t)(3 * w + i)]};
+      rgbe_to_float(rgb_out + 3 * (j * w + i), q);
+    }
+  }
+  return MCPT_OK;
+}
+
 extern "C" int mcpt_write_hdr(const char *path, int32_t width, int32_t height, const float *rgba,
                               int32_t flip) {
   if (!path) return fail(MCPT_ERR_ARG, "write_hdr: null path");

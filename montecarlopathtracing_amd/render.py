@@ -451,6 +451,43 @@ class Renderer:
         L.check(L.lib().mcpt_gamma_preview(self.ctx, L.ptr(color), L.ptr(out), color.numel() // 4, _stream()))
         return out.view(-1, 4)
 
+    # ------------------------------------------- environment lighting (opt-in)
+    def set_environment(self, scene, scale=(1.0, 1.0, 1.0), map=None, rotate=0.0):
+        """mcpt_scene_set_environment: a ray that leaves `scene` picks up
+        scale * map(direction) instead of black.  `scale`: a number or (r, g, b),
+        finite and >= 0; `map`: None (a constant environment) or a lat-long
+        image (height, width, 3) float32, row 0 the top (scene.read_hdr's
+        layout), finite and >= 0; `rotate`: degrees about +Y.  Replaces a
+        previous environment; the primary-hit cache stays valid."""
+        s = np.broadcast_to(np.asarray(scale, np.float32), (3,)) if np.ndim(scale) == 0 else np.asarray(scale, np.float32)
+        if s.shape != (3,):
+            raise ValueError("set_environment: scale is a number or (r, g, b)")
+        e = L.Environment()
+        e.scale[0], e.scale[1], e.scale[2], e.scale[3] = float(s[0]), float(s[1]), float(s[2]), 0.0
+        e.rotate_deg = float(rotate)
+        m = None
+        if map is not None:
+            m = np.ascontiguousarray(map, np.float32)
+            if m.ndim != 3 or m.shape[2] != 3 or m.size == 0:
+                raise ValueError("set_environment: map is (height, width, 3), height and width at least 1")
+            e.map_rgb = m.ctypes.data
+            e.height, e.width = m.shape[0], m.shape[1]
+        L.check(L.lib().mcpt_scene_set_environment(self.ctx, scene.handle, ctypes.byref(e)))
+
+    def clear_environment(self, scene):
+        """Back to the reference's black for rays that miss (the bits of a
+        scene whose environment was never set)."""
+        L.check(L.lib().mcpt_scene_set_environment(self.ctx, scene.handle, None))
+
+    def env_eval(self, scene, rays):
+        """mcpt_env_eval: the scene's environment radiance for every record of
+        a Ray buffer (device bytes), a float32 (n, 4) device tensor (rgb, 0);
+        zeros without an environment.  With generate_rays: a background plate."""
+        n = rays.numel() * rays.element_size() // L.RAY.itemsize
+        out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        L.check(L.lib().mcpt_env_eval(self.ctx, scene.handle, L.ptr(rays), n, L.ptr(out), _stream()))
+        return out
+
     # ------------------------------------------------------ denoise (opt-in)
     def first_hits(self, scene, camera, width, height, mode=L.MODE_EXACT):
         """Every pixel's first hit (W*H Hit records, device bytes): generate_rays

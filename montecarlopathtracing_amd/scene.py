@@ -90,6 +90,26 @@ def write_hdr(path, rgba, flip=True):
     L.check(L.lib().mcpt_write_hdr(path.encode(), a.shape[1], a.shape[0], L.ptr(a), int(flip)))
 
 
+def decode_hdr(data):
+    """Radiance RGBE bytes -> (height, width, 3) float32, rows in file order
+    (mcpt_decode_hdr: RLE and flat scanlines, decoded as stb_image does).  A
+    malformed file raises MCPTError."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    w, h = ctypes.c_int32(0), ctypes.c_int32(0)
+    lib = L.lib()
+    L.check(lib.mcpt_decode_hdr(L.ptr(buf), len(buf), ctypes.byref(w), ctypes.byref(h), None, 0))
+    out = np.zeros((h.value, w.value, 3), np.float32)
+    L.check(lib.mcpt_decode_hdr(L.ptr(buf), len(buf), ctypes.byref(w), ctypes.byref(h), L.ptr(out), out.size))
+    return out
+
+
+def read_hdr(path):
+    """A .hdr file as (height, width, 3) float32, row 0 the file's first
+    (its top): the layout Renderer.set_environment takes as a map."""
+    with open(path, "rb") as fh:
+        return decode_hdr(fh.read())
+
+
 def preview_rgb8(preview, flip=True):
     """8-bit RGB of a gamma-encoded preview (mcpt_gamma_preview's float4s):
     round(clamp(c, 0, 1) * 255) per channel; flip=True puts the image's top
