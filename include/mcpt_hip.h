@@ -377,7 +377,18 @@ int mcpt_scene_read(const mcpt_scene *scene, int32_t which, void *host, int64_t 
  * The history rule is untouched: a jittered pixel is still the reference's
  * mean over its non-zero samples.  Such a call neither reads nor builds the
  * primary-hit cache (mcpt_stats.primary_cache = 0) and leaves a held one
- * valid for later unjittered calls.                                      */
+ * valid for later unjittered calls.
+ * Where MCPT_MODE_EXACT may differ from the reference: a segment whose ray
+ * has a direction component with 0 < |d| < 2^-126 (denormal, not zero) AND
+ * its origin exactly on a box plane of the tree on that axis; there the
+ * hoisted rcp(d) = +-inf makes the slab test 0 * inf = NaN where the
+ * reference computes 0 / d = 0, and a triangle the reference accepts can be
+ * missed.  Every other ray holds the reference's bits; MCPT_MODE_NOPRUNE
+ * holds them on all rays (both measured on k_render and the primary-hit
+ * pass: tests/test_gpu_intersect_edges.py, test_render_denormal_directions).  generateRay and shade.cl normalize every
+ * direction, so such a component needs a camera `direction` (or a bounce)
+ * with a component below 2^-126 of the largest one.  mcpt_intersect has no
+ * such exception (it tests each ray and searches these literally).        */
 int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam,
                        const mcpt_render_params *params, uint32_t *seeds_dev,
                        float *hist_dev, int32_t *count_dev, void *stream);
@@ -419,7 +430,15 @@ int mcpt_generate_rays(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t width, int
  * advanced seed back to, seeds_dev[idy * width + idx].                     */
 int mcpt_generate_rays_jittered(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t width, int32_t height,
                                 uint32_t *seeds_dev, mcpt_ray *rays_dev, void *stream);
-/* intersect.cl intersectRays (tmin = EPSILON 1e-3, oclbasic.h:193)        */
+/* intersect.cl intersectRays (tmin = EPSILON 1e-3, oclbasic.h:193)
+ * Arbitrary rays (a unit direction is the callers' convention, not a
+ * requirement).  MCPT_MODE_EXACT gives the reference kernel's t, normal,
+ * point and material_id for every live ray whose direction components are
+ * finite: a ray with a component 0 < |d| < 2^-126 (denormal, not zero), the
+ * one class on which the hoisted rcp(d) differs from the reference's
+ * division, is searched with the literal division.
+ * Measured up to |d| = 1 only: a component above 2^126, whose reciprocal is
+ * denormal, is outside what tests/test_gpu_intersect_edges.py shoots.      */
 int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays_dev,
                    int64_t n, mcpt_hit *hits_dev, float tmin, int32_t mode, void *stream);
 /* shade.cl shade (-D MAX_DEPTH)                                           */

@@ -314,9 +314,12 @@ struct Trace {
 
 template <bool LITERAL>
 __device__ inline BoxT box_test(f3 bmin, f3 bmax, f3 o, f3 d, f3 rinv) {
-  if (LITERAL) {  // objdef.h:227-228 verbatim: (bb - o) / d
-    f3 t1 = (bmin - o) / d;
-    f3 t2 = (bmax - o) / d;
+  if (LITERAL) {  // objdef.h:227-228: (bb - o) / d, the 2.5-ulp division written out (cl_div): as a plain
+    // '/' the root box's six divisions lost their !fpmath and were compiled correctly rounded, one ulp
+    // off the reference's on a ray that leaves the root box through an edge (test_gpu_intersect_edges)
+    const f3 x1 = bmin - o, x2 = bmax - o;
+    f3 t1 = (f3){cl_div(x1.x, d.x), cl_div(x1.y, d.y), cl_div(x1.z, d.z)};
+    f3 t2 = (f3){cl_div(x2.x, d.x), cl_div(x2.y, d.y), cl_div(x2.z, d.z)};
     BoxT r;
     r.tnear = fmaxf(fmaxf(fminf(t1.x, t2.x), fminf(t1.y, t2.y)), fminf(t1.z, t2.z));
     r.tfar = fminf(fminf(fmaxf(t1.x, t2.x), fmaxf(t1.y, t2.y)), fmaxf(t1.z, t2.z));
@@ -452,6 +455,15 @@ __device__ inline void near_update(float t, float &t1, float &t2) {  // selects,
   t1 = lt1 ? t : t1;
 }
 __device__ inline bool near_ambiguous(float t1, float t2) { return t2 < kFltMax && !(t2 - t1 >= kEps); }
+
+// true when a component of d is denormal but not zero (0 < |d| < 2^-126), read
+// from the bits: the one class of finite directions for which hoisting
+// rcp(d) out of the slab test changes it.
+__device__ inline bool denormal_component(f3 d) {
+  const uint32_t x = (uint32_t)as_i(d.x), y = (uint32_t)as_i(d.y), z = (uint32_t)as_i(d.z);
+  auto den = [](uint32_t b) { return (b & 0x7F800000u) == 0u && (b & 0x007FFFFFu) != 0u; };
+  return den(x) || den(y) || den(z);
+}
 
 // NOPRUNE: the reference's exhaustive left-first DFS of objdef.h:240-275 on
 // its binary tree with the literal division.
@@ -1565,8 +1577,16 @@ __global__ void __launch_bounds__(64) k_intersect(SceneView S, const mcpt_ray *r
   const f4 d = *(const f4 *)rays[id].direction;
   if (as_i(o.w) & (int32_t)0xFF000000) return;  // intersect.cl:16-18 (hit left untouched)
   uint32_t fallbacks = 0;
-  Trace tr = MODE == MCPT_MODE_NOPRUNE ? traverse_noprune(S, o.xyz, d.xyz, tmin, lds_stack + threadIdx.x, 64)
-                                       : traverse_exact(S, o.xyz, d.xyz, tmin, lds_stack + threadIdx.x, 64, fallbacks);
+  // A direction component with 0 < |d| < 2^-126: v_rcp_f32 flushes it and gives
+  // +-inf, so with the origin exactly on a box plane on that axis the EXACT
+  // slab test computes 0 * inf = NaN (the box fails) where the reference's
+  // (bb - o) / d is 0 (the box passes) -- and the box's triangle can be one
+  // the reference accepts (measured: tests/test_gpu_intersect_edges.py,
+  // edge/tinydir).  Such a ray takes the literal-division search; one test
+  // per ray, outside the search loop.
+  const bool literal = MODE == MCPT_MODE_NOPRUNE || denormal_component(d.xyz);
+  Trace tr = literal ? traverse_noprune(S, o.xyz, d.xyz, tmin, lds_stack + threadIdx.x, 64)
+                     : traverse_exact(S, o.xyz, d.xyz, tmin, lds_stack + threadIdx.x, 64, fallbacks);
   mcpt_hit h;
   f4 nrm = (f4){0.0f, 0.0f, 0.0f, 0.0f}, pt = (f4){0.0f, 0.0f, 0.0f, 0.0f};
   h.t = tr.t;
@@ -2904,7 +2924,9 @@ int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays,
   if (!ctx || !scene || !rays || !hits || n < 0) return mcpt::fail(MCPT_ERR_ARG, "intersect: bad argument");
   if (n == 0) return MCPT_OK;
   HIP_OK(hipSetDevice(ctx->device));
-  size_t lds = (size_t)(mode == MCPT_MODE_NOPRUNE ? scene->stack_depth : scene->stack_depth4) * 64 * sizeof(int32_t);
+  // EXACT: a ray with a denormal direction component takes the literal search, on the binary tree's stack
+  size_t lds = (size_t)(mode == MCPT_MODE_NOPRUNE ? scene->stack_depth : std::max(scene->stack_depth, scene->stack_depth4)) *
+               64 * sizeof(int32_t);
   dim3 g((unsigned)((n + 63) / 64));
   if (mode == MCPT_MODE_NOPRUNE)
     hipLaunchKernelGGL(k_intersect<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,

@@ -334,7 +334,11 @@ __device__ inline TriHit cramer_reduced(f3 rd, f3 nab, f3 nac, f3 aro, f3 realn,
 // intersectAABB (objdef.h:223-237).  (bb - o) / d under the 2.5-ulp OpenCL
 // division is ldexp(mant(x) * rcp(mant(d)), ex - ed) == x * rcp(d) for every
 // normal-range quotient; rcp(d) is hoisted per ray (verified on the GPU
-// against the literal division, tests/test_gpu_parity.py).
+// against the literal division by tests/test_gpu_intersect_edges.py: the
+// edge/axis and edge/tinydir families and the scenes scaled by 2^-20 and
+// 2^20).  Not for 0 < |d| < 2^-126, where rcp(d) is +-inf and 0 * inf is NaN
+// against the reference's 0 / d = 0: mcpt_intersect searches such a ray
+// with the literal division, mcpt_render_frames documents the exception.
 struct BoxT {
   float tnear, tfar;
 };
