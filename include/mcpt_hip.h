@@ -212,8 +212,13 @@ typedef struct mcpt_tuning {
                                the wave claims and starts them together (1)    */
   int32_t quantized;        /* EXACT search tree: 0 auto (the 64-B quantized
                                nodes when the 128-B tree exceeds 32 MiB, the
-                               GPU's aggregate L2), 1 quantized whenever the
-                               scene has them, 2 the 128-B nodes                 */
+                               GPU's aggregate L2; the 96-B exact nodes for
+                               trees over 1 MiB up to that; the 128-B nodes
+                               below), 1 quantized whenever the
+                               scene has them, 2 the 128-B nodes, 3 the 96-B
+                               exact nodes whenever the scene has them (trees
+                               up to 32 MiB; six gathers a node step, not
+                               seven)                                            */
   int32_t primary_cache;    /* every frame re-shoots the same primary ray, so its
                                hit is computed once per (scene, camera, image,
                                stripes, mode) and kept in the context: 0 auto
@@ -354,7 +359,10 @@ int mcpt_scene_upload_device(mcpt_ctx *ctx, const mcpt_triangle *tris_dev, int64
 /* A scene's device arrays copied to the host (introspection).  which: 0 the
  * search tree (128-B nodes), 1 its quantized nodes, 2 the reference tree
  * 4-wide, 3 the binary child-box nodes, 4 triangles, 5 quantized-path
- * triangles, 6 int32[4] {stack_depth, stack_depth4, quantized, n_internal}.
+ * triangles, 6 int32[4] {stack_depth, stack_depth4, quantized, n_internal},
+ * 7 the 96-B search-tree nodes, 8 their slot-indexed triangles, 9 the
+ * reference tree 4-wide with its leaves relabelled to those (7-9: 0 bytes
+ * where the scene has none).
  * *bytes = the size (host NULL: size only).                               */
 int mcpt_scene_read(const mcpt_scene *scene, int32_t which, void *host, int64_t cap, int64_t *bytes);
 
@@ -399,6 +407,10 @@ int mcpt_get_tuning(mcpt_ctx *ctx, mcpt_tuning *out);
 /* Forget the primary-hit cache (mcpt_tuning.primary_cache): the next render
  * call traces or recomputes its primary hits itself (bench.py's timed call). */
 int mcpt_drop_caches(mcpt_ctx *ctx);
+/* The search-tree node format of the last render call: 0 the 128-B nodes (and
+ * NOPRUNE's binary tree), 1 the 64-B quantized nodes (mcpt_stats.quantized),
+ * 2 the 96-B exact nodes.  A new entry point; no struct changes.            */
+int mcpt_get_node_format(mcpt_ctx *ctx, int32_t *out);
 
 /* Per-image state in HBM for C/C++ hosts that do not manage device memory
  * themselves: the reference's randBuffer (scenebuild.cpp:113-120),

@@ -120,6 +120,7 @@ SIGNATURES = {
     "mcpt_set_tuning": (_I32, [_P, _P]),
     "mcpt_get_tuning": (_I32, [_P, _P]),
     "mcpt_drop_caches": (_I32, [_P]),
+    "mcpt_get_node_format": (_I32, [_P, _P]),
     "mcpt_state_create": (_I32, [_P, _I32, _I32, _P, _P]),
     "mcpt_state_buffers": (_I32, [_P, _P, _P, _P]),
     "mcpt_download": (_I32, [_P, _P, _P, _P, _P, _P]),

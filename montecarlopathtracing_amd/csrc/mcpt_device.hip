@@ -38,6 +38,7 @@
 #include "../../include/mcpt_hip.h"
 #include "mcpt_refmath.h"
 #include "mcpt_bvh4.h"
+#include "mcpt_node96.h"  // the 96-B exact search-tree node and its slot-indexed triangles
 #include "mcpt_plan.h"  // the launch plan and its constants (kHandoffWords, kHandoffMaxBytes, ...)
 #include "mcpt_queue.h"  // queue entries, block frames, the hand-off record, the wave's queue state
 #include "mcpt_upload.h"
@@ -133,6 +134,7 @@ static_assert(sizeof(DevTriQ) == 64, "64-B triangle");
 constexpr int32_t kDone = INT32_MIN;           // traversal finished
 constexpr int32_t kPop = INT32_MIN + 1;        // take the next entry from the stack
 constexpr int32_t kEmptySlot = INT32_MIN + 2;  // unused 4-wide slot
+constexpr int kFmt128 = 0, kFmtQ = 1, kFmt96 = 2;  // k_render's search-tree node formats
 static_assert(kEmptySlot == mcpt::kEmptySlot4, "one empty-slot marker");
 
 struct SceneView {
@@ -162,6 +164,11 @@ struct mcpt_scene {
   DevNode4Q *near4q = nullptr;
   DevTriQ *triq = nullptr;
   int64_t near4_bytes = 0;  // the 128-B search tree's size (auto choice of the quantized one)
+  // the 96-B form of near4 (mcpt_node96.h; nullptr: not built), nodes4 with its
+  // leaf links relabelled to tri4 indices, and the slot-indexed triangles
+  mcpt::Node96 *near4x = nullptr;
+  DevNode4 *nodes4x = nullptr;
+  DevTri *tri4 = nullptr;
   mcpt_material *mats = nullptr;
   int64_t n_tris = 0, n_internal = 0;
   int32_t n_mats = 0;
@@ -179,6 +186,10 @@ constexpr int kQueues = 8;         // k_render work queues (at most): one per XC
 constexpr int kQueueStride = 32;   // u32 words between queue heads: one 128-B line each
 constexpr int kStatSlots = 24;
 constexpr int64_t kQuantAutoBytes = 32ll << 20;  // 8 XCDs x 4 MiB of L2
+// mcpt_tuning.quantized 0 takes the 96-B nodes for search trees over this size, up to kQuantAutoBytes: C2's
+// 2.1 MB tree +4.9 % Msamples/s, C4's +6.6 %, C3's 0.24 MB tree even (-0.5 %, inside its spread) and so left
+// on the 128-B nodes (profiles/node96_ab*.jsonl)
+constexpr int64_t kNode96AutoMinBytes = 1ll << 20;
 // primary-hit pass: k_primary (one ray per lane) for search trees up to this
 // size, k_render's PRIM form (batched phases, resident grid) beyond: C3's
 // 0.24 MB tree 0.07 vs 0.13 ms, C2's 2.1 MB 0.18 vs 0.15, C5's 435 MB 3.57 vs
@@ -265,6 +276,7 @@ struct mcpt_ctx {
   };
   std::vector<Occ> occ;                   // occupancy per (kernel, LDS bytes), queried once
   mcpt_stats last;
+  int32_t last_node_format = 0;           // mcpt_get_node_format
   bool last_pending = false;              // the last render call's events/counters not read yet
   bool last_stats = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -392,7 +404,9 @@ struct WindowStack {
 // passing slot, i.e. the reference's left-first DFS.  The other passing slots
 // are pushed so that they pop in slot order.  Returns the slot's link (an
 // internal node or ~triangle) or kPop.
-template <bool PRUNE, class Stk>
+// LINK_EMPTY false (the 96-B nodes): an empty slot is a box that is never
+// entered (mcpt_node96.h), no link compare.
+template <bool PRUNE, bool LINK_EMPTY = true, class Stk>
 __device__ inline int32_t step4q(f4 q0, f4 q1, f4 q2, f4 q3, f4 q4, f4 q5, int32_t l0, int32_t l1, int32_t l2,
                                  int32_t l3, f3 o, f3 rinv, float tmin, float lim, bool nearest, const Stk &stk, int &sp,
                                  uint32_t &nodes_ctr);
@@ -402,7 +416,7 @@ __device__ inline int32_t step4(const DevNode4 &N, f3 o, f3 rinv, float tmin, fl
   return step4q<PRUNE>(N.q[0], N.q[1], N.q[2], N.q[3], N.q[4], N.q[5], N.link[0], N.link[1], N.link[2], N.link[3], o,
                        rinv, tmin, lim, nearest, stk, sp, nodes_ctr);
 }
-template <bool PRUNE, class Stk>
+template <bool PRUNE, bool LINK_EMPTY, class Stk>
 __device__ inline int32_t step4q(f4 q0, f4 q1, f4 q2, f4 q3, f4 q4, f4 q5, int32_t l0, int32_t l1, int32_t l2,
                                  int32_t l3, f3 o, f3 rinv, float tmin, float lim, bool nearest, const Stk &stk, int &sp,
                                  uint32_t &nodes_ctr) {
@@ -410,8 +424,9 @@ __device__ inline int32_t step4q(f4 q0, f4 q1, f4 q2, f4 q3, f4 q4, f4 q5, int32
   BoxT b1 = slab_pairs(q1.zw, q2.xy, q2.zw, o, rinv);
   BoxT b2 = slab_pairs(q3.xy, q3.zw, q4.xy, o, rinv);
   BoxT b3 = slab_pairs(q4.zw, q5.xy, q5.zw, o, rinv);
-  bool h0 = slab_pass(b0, tmin) && l0 != kEmptySlot, h1 = slab_pass(b1, tmin) && l1 != kEmptySlot;
-  bool h2 = slab_pass(b2, tmin) && l2 != kEmptySlot, h3 = slab_pass(b3, tmin) && l3 != kEmptySlot;
+  static_assert(LINK_EMPTY || PRUNE, "an empty 96-B slot is kept out by the slab test or the pruning limit");
+  bool h0 = slab_pass(b0, tmin) && (!LINK_EMPTY || l0 != kEmptySlot), h1 = slab_pass(b1, tmin) && (!LINK_EMPTY || l1 != kEmptySlot);
+  bool h2 = slab_pass(b2, tmin) && (!LINK_EMPTY || l2 != kEmptySlot), h3 = slab_pass(b3, tmin) && (!LINK_EMPTY || l3 != kEmptySlot);
   if (PRUNE) {
     h0 = h0 && !(b0.tnear > lim);
     h1 = h1 && !(b1.tnear > lim);
@@ -434,6 +449,28 @@ __device__ inline int32_t step4q(f4 q0, f4 q1, f4 q2, f4 q3, f4 q4, f4 q5, int32
   if (h1 && sel != 1) stk.push(sp, l1);
   if (h0 && sel != 0) stk.push(sp, l0);
   return nxt;
+}
+// The four stack codes of 96-B node n (mcpt_node96.h, n96_link): the first
+// child's id from the low bytes of slot 0's miny, maxy, minz (two v_perm_b32),
+// a slot's type from the order of its x pair; slot k's code is the child base
+// or the leaf base ~(4n + 3), plus k.
+__device__ inline void links96(f4 q0, f4 q1, f4 q3, f4 q4, int32_t n, int32_t &l0, int32_t &l1, int32_t &l2,
+                               int32_t &l3) {
+  const uint32_t lo = __builtin_amdgcn_perm(as_u(q0.w), as_u(q0.z), 0x0c0c0400u);
+  const int32_t base = (int32_t)__builtin_amdgcn_perm(as_u(q1.x), lo, 0x0c040100u);
+  const int32_t lb = ~(4 * n + 3);
+  l0 = q0.x > q0.y ? base : lb;
+  l1 = (q1.z > q1.w ? base : lb) + 1;
+  l2 = (q3.x > q3.y ? base : lb) + 2;
+  l3 = (q4.z > q4.w ? base : lb) + 3;
+}
+template <bool PRUNE, class Stk>
+__device__ inline int32_t step96(f4 q0, f4 q1, f4 q2, f4 q3, f4 q4, f4 q5, int32_t n, f3 o, f3 rinv, float tmin,
+                                 float lim, const Stk &stk, int &sp, uint32_t &nodes_ctr, int32_t *first = nullptr) {
+  int32_t l0, l1, l2, l3;
+  links96(q0, q1, q3, q4, n, l0, l1, l2, l3);
+  if (first) *first = l0;
+  return step4q<PRUNE, false>(q0, q1, q2, q3, q4, q5, l0, l1, l2, l3, o, rinv, tmin, lim, true, stk, sp, nodes_ctr);
 }
 
 // MCPT_POW_LOBE 0: the Phong lobe calls ocml's pow (A/B builds only)
@@ -926,11 +963,18 @@ constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193,
 // E: the scene has an environment (mcpt_scene_set_environment): a segment that
 // misses ends its path with color * env_radiance(d) instead of black.  A
 // template parameter for J's reason: an unlit render runs the code it ran.
-template <int MODE, bool STATS, bool WIN, bool PAIR, bool Q, bool PRIM = false, bool G = true, bool J = false,
+// FMT: the EXACT search tree's node format: kFmt128 (128-B nodes), kFmtQ (64-B
+// quantized) or kFmt96 (96-B exact, mcpt_node96.h: the launch's S.near4 then
+// points at the 96-B array, S.nodes4 at the relabelled reference tree and
+// S.tris at tri4, so every stack entry and hit speaks tri4's indices).
+template <int MODE, bool STATS, bool WIN, bool PAIR, int FMT, bool PRIM = false, bool G = true, bool J = false,
           bool E = false>
 __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(RenderArgs A) {
   constexpr bool PRUNE = MODE != MCPT_MODE_NOPRUNE;
   constexpr bool LIT = MODE == MCPT_MODE_NOPRUNE;
+  constexpr bool Q = FMT == kFmtQ, X = FMT == kFmt96;
+  static_assert(!(X && (LIT || PRIM)), "the 96-B nodes are the EXACT shading forms'");
+  constexpr int TQ = X ? 6 : 7;  // 16-B quads of a top-level node in LDS
   static_assert(!(J && PRIM), "the primary-hit pass is the unjittered frame start's");
   static_assert(!(E && PRIM), "the primary-hit pass records hits, not radiance");
   static_assert(!(Q && LIT), "the quantized search tree is an EXACT-mode structure");
@@ -973,13 +1017,21 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
     // the top levels (the 128-B tree's; the quantized tree has the same ids and
     // links): lane-strided over the nodes' 16-B quads, node by node in layout
     // order; a slot's child id comes from its parent's links in global memory
-    for (int e = (int)threadIdx.x; e < n_top * 7; e += 64 * kWgWaves) {
-      const int i = e / 7, w = e % 7;
+    // (the 96-B nodes: six quads a node, the child id decoded from the parent's planes)
+    for (int e = (int)threadIdx.x; e < n_top * TQ; e += 64 * kWgWaves) {
+      const int i = e / TQ, w = e % TQ;
       int lv[kMaxTopLevels], nl = 0;  // the slots on the path from the root, deepest first
       for (int up = i; up > 0; up = (up - 1) >> 2) lv[nl++] = (up - 1) & 3;
       int32_t id = 0;  // layout node i's id, or < 0 (a leaf or an empty slot on the path)
-      for (int t = nl - 1; t >= 0 && id >= 0; --t) id = S.near4[id].link[lv[t]];
-      if (id >= 0) top4[i * 7 + w] = reinterpret_cast<const f4 *>(S.near4 + id)[w];
+      for (int t = nl - 1; t >= 0 && id >= 0; --t) {
+        if constexpr (X) {
+          const float *nq = reinterpret_cast<const float *>(S.near4) + (size_t)id * 24;
+          id = n96_slot_internal(nq, lv[t]) ? n96_first_child(nq) + lv[t] : -1;
+        } else {
+          id = S.near4[id].link[lv[t]];
+        }
+      }
+      if (id >= 0) top4[i * TQ + w] = (reinterpret_cast<const f4 *>(S.near4) + (size_t)id * (X ? 6 : 8))[w];
     }
   }
   typedef const __attribute__((address_space(3))) mcpt_material LdsMaterial;
@@ -1062,12 +1114,20 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
 #pragma unroll
       for (int lvl = 0; lvl < kMaxTopLevels; ++lvl) {
         if (lvl >= A.top_levels) break;
-        LdsF4 *rq = (LdsF4 *)(top4 + ti * 7);
-        const f4 q0 = rq[0], q1 = rq[1], q2 = rq[2], q3 = rq[3], q4 = rq[4], q5 = rq[5], lk = rq[6];
-        cur = step4q<PRUNE>(q0, q1, q2, q3, q4, q5, as_i(lk.x), as_i(lk.y), as_i(lk.z), as_i(lk.w), o.xyz, rinv, kTmin,
-                            best_t + S.prune_margin, true, sk, sp, ctr);
-        // the entered slot's child, when it is internal: the next level's node
-        const int k = cur < 0 ? -1 : (cur == as_i(lk.x) ? 0 : (cur == as_i(lk.y) ? 1 : (cur == as_i(lk.z) ? 2 : 3)));
+        LdsF4 *rq = (LdsF4 *)(top4 + ti * TQ);
+        const f4 q0 = rq[0], q1 = rq[1], q2 = rq[2], q3 = rq[3], q4 = rq[4], q5 = rq[5];
+        int k;  // the entered slot, when its child is internal: the next level's node
+        if constexpr (X) {
+          int32_t first;  // cur is this node's id; an internal child sits in slot (its id - the first child's)
+          cur = step96<PRUNE>(q0, q1, q2, q3, q4, q5, cur, o.xyz, rinv, kTmin, best_t + S.prune_margin, sk, sp, ctr,
+                              &first);
+          k = cur < 0 ? -1 : cur - first;
+        } else {
+          const f4 lk = rq[6];
+          cur = step4q<PRUNE>(q0, q1, q2, q3, q4, q5, as_i(lk.x), as_i(lk.y), as_i(lk.z), as_i(lk.w), o.xyz, rinv,
+                              kTmin, best_t + S.prune_margin, true, sk, sp, ctr);
+          k = cur < 0 ? -1 : (cur == as_i(lk.x) ? 0 : (cur == as_i(lk.y) ? 1 : (cur == as_i(lk.z) ? 2 : 3)));
+        }
         ti = k < 0 ? -1 : 4 * ti + 1 + k;
         if (ti < 0) break;
       }
@@ -1291,7 +1351,22 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
     if (__ballot(in_t)) {
       if (STATS && lane == __builtin_ctzll(__ballot(1))) w_t++;
       if (in_t) {
-        if (Q) {  // EXACT, quantized SAH tree nearest-first (4 loads), or the reference tree left-first
+        if constexpr (X) {  // EXACT, 96-B SAH tree nearest-first (6 loads), or the relabelled reference tree left-first
+          uint32_t ctr = 0;
+          if (MCPT_DCHECK(cur < (ref ? S.n_nodes4 : S.n_near4), 1)) {
+            if (!ref) {
+              const f4 *p = reinterpret_cast<const f4 *>(S.near4) + (size_t)cur * 6;
+              const f4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4], q5 = p[5];
+              cur = step96<PRUNE>(q0, q1, q2, q3, q4, q5, cur, o.xyz, rinv, kTmin, best_t + S.prune_margin, sk, sp, ctr);
+            } else {
+              cur = step4<PRUNE>(S.nodes4[cur], o.xyz, rinv, kTmin, best_t + S.prune_margin, false, sk, sp, ctr);
+            }
+            if (!MCPT_DCHECK(sp <= stack_cap, 0)) sp = stack_cap;
+          } else {
+            cur = kPop;
+          }
+          if (STATS) n_nodes += ctr;
+        } else if (Q) {  // EXACT, quantized SAH tree nearest-first (4 loads), or the reference tree left-first
           uint32_t ctr = 0;
           if (MCPT_DCHECK(cur < (ref ? S.n_nodes4 : S.n_near4), 1)) {
             f4 q0, q1, q2, q3, q4, q5;
@@ -2050,7 +2125,7 @@ int mcpt_get_entry_log(mcpt_ctx *c, uint32_t *out, int64_t cap_entries, int64_t 
 
 int mcpt_set_tuning(mcpt_ctx *c, const mcpt_tuning *t) {
   if (!c) return mcpt::fail(MCPT_ERR_ARG, "set_tuning: null ctx");
-  if (t && (t->stack_window < 0 || t->stack_window > 2 || t->quantized < 0 || t->quantized > 2 ||
+  if (t && (t->stack_window < 0 || t->stack_window > 2 || t->quantized < 0 || t->quantized > 3 ||
             t->primary_cache < 0 || t->primary_cache > 2 || t->lds_pad < 0 || t->lds_pad > 65536 ||
             t->queue_chunk > 4096 || t->leaf_threshold > 64 || t->shade_threshold > 64 || t->fetch_threshold > 64 ||
             t->last_block_frames < -1 || t->tile_order < 0 || t->tile_order > 2 || t->pixel_spread < 0 ||
@@ -2060,6 +2135,15 @@ int mcpt_set_tuning(mcpt_ctx *c, const mcpt_tuning *t) {
     c->tune = *t;
   else
     std::memset(&c->tune, 0, sizeof(c->tune));
+  return MCPT_OK;
+}
+
+// The search-tree node format of the last render call (the value mcpt_stats'
+// `quantized` cannot carry): 0 the 128-B nodes (and NOPRUNE's binary tree),
+// 1 the 64-B quantized nodes, 2 the 96-B exact nodes.
+int mcpt_get_node_format(mcpt_ctx *c, int32_t *out) {
+  if (!c || !out) return mcpt::fail(MCPT_ERR_ARG, "get_node_format: null");
+  *out = c->last_node_format;
   return MCPT_OK;
 }
 
@@ -2342,6 +2426,159 @@ static void finish_scene(mcpt_scene *s, uint64_t uid, int64_t n_tris, int64_t n_
   v.prune_margin = std::isfinite(diag) ? std::ldexp(diag, -10) : __builtin_inff();
 }
 
+// ---- the 96-B search tree (mcpt_node96.h), derived from the finished near4,
+// nodes4 and tris by either upload path: the same per-node functions in a host
+// loop or in small kernels, so the same bytes.  new id of a node = first[its
+// parent] + its rank among the parent's internal slots, first[p] = 1 + the
+// internal slots of all nodes before p.
+static bool node96_fits(int64_t n_near4, const mcpt_bvh_node &root) {
+  if (n_near4 <= 0 || n_near4 > mcpt::kNode96MaxNodes || n_near4 * (int64_t)sizeof(DevNode4) > kQuantAutoBytes)
+    return false;  // (larger trees take the quantized nodes)
+  for (int a = 0; a < 3; ++a)
+    if (!(std::fabs(root.bbmin[a]) < mcpt::kNode96MaxPlane && std::fabs(root.bbmax[a]) < mcpt::kNode96MaxPlane))
+      return false;
+  return true;
+}
+// one tri4 record: the reference triangle's DevTri with its id in aux.y, or zeros
+__host__ __device__ inline DevTri tri4_record(const DevTri *tris, int32_t t) {
+  DevTri r;
+  if (t < 0) {
+    r.v0 = r.nab = r.nac = r.aux = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+  } else {
+    r = tris[t];
+    r.aux.y = mcpt::n96_float((uint32_t)t);
+  }
+  return r;
+}
+// converts near4 node p into near4x[newid[p]] and its four tri4 records
+__host__ __device__ inline void node96_emit(const mcpt::Node4Rec *near4, int32_t p, const int32_t *first,
+                                            const int32_t *newid, const DevTri *tris, mcpt::Node96 *near4x,
+                                            DevTri *tri4, int32_t *tri4_of) {
+  int32_t leaf_tri[4];
+  const int32_t self = newid[p];
+  mcpt::n96_convert(near4[p], first[p], near4x[self], leaf_tri);
+  for (int j = 0; j < 4; ++j) {
+    tri4[4 * (int64_t)self + j] = tri4_record(tris, leaf_tri[j]);
+    if (leaf_tri[j] >= 0) tri4_of[leaf_tri[j]] = 4 * self + j;
+  }
+}
+__global__ void k_n96_count(const mcpt::Node4Rec *near4, int32_t n, int32_t *cnt) {
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p < n) cnt[p] = mcpt::n96_count_internal(near4[p]);
+}
+__global__ void k_n96_ids(const mcpt::Node4Rec *near4, int32_t n, const int32_t *first, int32_t *newid) {
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p < n) mcpt::n96_assign_ids(near4, p, n, first, newid);
+}
+__global__ void k_n96_emit(const mcpt::Node4Rec *near4, int32_t n, const int32_t *first, const int32_t *newid,
+                           const DevTri *tris, int32_t n_tris, mcpt::Node96 *near4x, DevTri *tri4, int32_t *tri4_of) {
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n || newid[p] < 0 || newid[p] >= n) return;
+  for (int k = 0; k < 4; ++k)  // a leaf link past the triangle array: leave the node out (upload validates trees)
+    if (mcpt::n96_link_leaf(near4[p].link[k]) && ~near4[p].link[k] >= n_tris) return;
+  node96_emit(near4, p, first, newid, tris, near4x, tri4, tri4_of);
+}
+__global__ void k_n96_relabel(const mcpt::Node4Rec *nodes4, int32_t n4, const int32_t *tri4_of, int32_t n_tris,
+                              mcpt::Node4Rec *nodes4x) {
+  const int32_t p = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (p >= n4) return;
+  for (int k = 0; k < 4; ++k)
+    if (mcpt::n96_link_leaf(nodes4[p].link[k]) && ~nodes4[p].link[k] >= n_tris) return;
+  mcpt::n96_relabel(nodes4[p], tri4_of, nodes4x[p]);
+}
+// A single-triangle scene (root_leaf): no tree is searched; tri4[0] is the triangle.
+static void node96_root_leaf(const DevTri &t, int32_t tri, std::vector<mcpt::Node96> &nx, std::vector<DevTri> &t4) {
+  nx.resize(1);
+  for (float &q : nx[0].q) q = __builtin_inff();
+  t4.assign(4, tri4_record(nullptr, -1));
+  t4[0] = t;
+  t4[0].aux.y = mcpt::n96_float((uint32_t)tri);
+}
+// Host path.  Returns false when the scene keeps the 128-B nodes only.
+static bool node96_host(const std::vector<mcpt::Node4Rec> &near, const std::vector<DevNode4> &dn4,
+                        const std::vector<DevTri> &dt, const mcpt_bvh_node &root, std::vector<mcpt::Node96> &nx,
+                        std::vector<DevNode4> &n4x, std::vector<DevTri> &t4) {
+  if (!node96_fits((int64_t)near.size(), root)) return false;
+  n4x = dn4;
+  if (root.left == root.right) {
+    node96_root_leaf(dt[root.left], root.left, nx, t4);
+    return true;
+  }
+  const int32_t n = (int32_t)near.size();
+  std::vector<int32_t> cnt(n), first, newid(n, -1), tri4_of(dt.size(), -1);
+  for (int32_t p = 0; p < n; ++p) cnt[p] = mcpt::n96_count_internal(near[p]);
+  if (!mcpt::n96_first(cnt, first)) return false;
+  for (int32_t p = 0; p < n; ++p) mcpt::n96_assign_ids(near.data(), p, n, first.data(), newid.data());
+  nx.resize(n);
+  t4.resize(4 * (size_t)n);
+  for (int32_t p = 0; p < n; ++p)
+    node96_emit(near.data(), p, first.data(), newid.data(), dt.data(), nx.data(), t4.data(), tri4_of.data());
+  for (size_t p = 0; p < dn4.size(); ++p)
+    mcpt::n96_relabel(reinterpret_cast<const mcpt::Node4Rec &>(dn4[p]), tri4_of.data(),
+                      reinterpret_cast<mcpt::Node4Rec &>(n4x[p]));
+  return true;
+}
+// Device path: the scene's arrays are in *s already.  A scene that does not fit
+// keeps the 128-B nodes (s->near4x stays null); only a HIP failure is an error.
+static int node96_device(mcpt_scene *s, int64_t n_near4, int64_t n_nodes4, int64_t n_tris, const mcpt_bvh_node &root,
+                         hipStream_t st) {
+  if (!node96_fits(n_near4, root) || n_tris > INT32_MAX / 4) return MCPT_OK;
+  const int32_t n = (int32_t)n_near4, n4 = (int32_t)n_nodes4;
+  int32_t *d_int = nullptr;  // cnt / first [n], newid [n], tri4_of [n_tris]
+  auto done = [&](int rc) {
+    if (d_int) (void)hipFree(d_int);
+    if (rc != MCPT_OK)
+      for (void **a : {(void **)&s->near4x, (void **)&s->nodes4x, (void **)&s->tri4})
+        if (*a) (void)hipFree(*a), *a = nullptr;
+    return rc;
+  };
+#define N96_OK(expr) do { if ((expr) != hipSuccess) return done(mcpt::fail(MCPT_ERR_HIP, "scene_upload_device: " #expr)); } while (0)
+  N96_OK(hipMalloc(&s->near4x, (size_t)n * sizeof(mcpt::Node96)));
+  N96_OK(hipMalloc(&s->tri4, 4 * (size_t)n * sizeof(DevTri)));
+  if (n4 > 0) N96_OK(hipMalloc(&s->nodes4x, (size_t)n4 * sizeof(DevNode4)));
+  if (root.left == root.right) {
+    std::vector<mcpt::Node96> nx;
+    std::vector<DevTri> t4;
+    DevTri t;
+    N96_OK(hipMemcpyAsync(&t, s->tris + root.left, sizeof t, hipMemcpyDeviceToHost, st));
+    N96_OK(hipStreamSynchronize(st));
+    node96_root_leaf(t, root.left, nx, t4);
+    N96_OK(hipMemcpyAsync(s->near4x, nx.data(), sizeof(mcpt::Node96), hipMemcpyHostToDevice, st));
+    N96_OK(hipMemcpyAsync(s->tri4, t4.data(), 4 * sizeof(DevTri), hipMemcpyHostToDevice, st));
+    if (n4 > 0) N96_OK(hipMemcpyAsync(s->nodes4x, s->nodes4, (size_t)n4 * sizeof(DevNode4), hipMemcpyDeviceToDevice, st));
+    N96_OK(hipStreamSynchronize(st));
+    return done(MCPT_OK);
+  }
+  N96_OK(hipMalloc(&d_int, (2 * (size_t)n + (size_t)n_tris) * sizeof(int32_t)));
+  int32_t *d_first = d_int, *d_newid = d_int + n, *d_tri4_of = d_int + 2 * (size_t)n;
+  const mcpt::Node4Rec *near4 = reinterpret_cast<const mcpt::Node4Rec *>(s->near4);
+  const dim3 blk(256), grid((unsigned)((n + 255) / 256)), grid4((unsigned)((std::max(n4, 1) + 255) / 256));
+  N96_OK(hipMemsetAsync(d_int, 0xFF, (2 * (size_t)n + (size_t)n_tris) * sizeof(int32_t), st));  // -1: not assigned
+  N96_OK(hipMemsetAsync(s->near4x, 0, (size_t)n * sizeof(mcpt::Node96), st));
+  N96_OK(hipMemsetAsync(s->tri4, 0, 4 * (size_t)n * sizeof(DevTri), st));
+  hipLaunchKernelGGL(k_n96_count, grid, blk, 0, st, near4, n, d_first);
+  std::vector<int32_t> cnt(n), first;
+  N96_OK(hipMemcpyAsync(cnt.data(), d_first, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  N96_OK(hipStreamSynchronize(st));
+  if (!mcpt::n96_first(cnt, first)) {  // not a tree of n nodes: keep the 128-B nodes
+    (void)done(MCPT_ERR_HIP);
+    return MCPT_OK;
+  }
+  N96_OK(hipMemcpyAsync(d_first, first.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_n96_ids, grid, blk, 0, st, near4, n, d_first, d_newid);
+  hipLaunchKernelGGL(k_n96_emit, grid, blk, 0, st, near4, n, d_first, d_newid, s->tris, (int32_t)n_tris, s->near4x,
+                     s->tri4, d_tri4_of);
+  if (n4 > 0) {
+    N96_OK(hipMemcpyAsync(s->nodes4x, s->nodes4, (size_t)n4 * sizeof(DevNode4), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_n96_relabel, grid4, blk, 0, st, reinterpret_cast<const mcpt::Node4Rec *>(s->nodes4), n4,
+                       d_tri4_of, (int32_t)n_tris, reinterpret_cast<mcpt::Node4Rec *>(s->nodes4x));
+  }
+  N96_OK(hipGetLastError());
+  N96_OK(hipStreamSynchronize(st));
+#undef N96_OK
+  return done(MCPT_OK);
+}
+
 int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, const mcpt_bvh_node *nodes,
                       int64_t n_nodes, const mcpt_material *mats, int32_t n_mats, mcpt_scene **out) {
   if (!ctx || !tris || !nodes || !mats || !out || n_tris <= 0 || n_mats <= 0)
@@ -2370,6 +2607,10 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
   std::vector<DevNode4Q> nq;
   std::vector<DevTriQ> tq;
   const bool quant = quantize_tree(tris, n, nodes, n_nodes, n_int, near, dt, nq, tq);
+  std::vector<mcpt::Node96> nx;
+  std::vector<DevNode4> n4x;
+  std::vector<DevTri> t4;
+  const bool x96 = node96_host(near, dn4, dt, nodes[0], nx, n4x, t4);
 
   HIP_OK(hipSetDevice(ctx->device));
   mcpt_scene *s = new mcpt_scene();
@@ -2382,7 +2623,10 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
       !put(&s->nodes, dn.data(), dn.size() * sizeof(DevNode)) || !put(&s->tris, dt.data(), dt.size() * sizeof(DevTri)) ||
       !put(&s->mats, mats, n_mats * sizeof(mcpt_material)) ||
       (quant && (!put(&s->near4q, nq.data(), nq.size() * sizeof(DevNode4Q)) ||
-                 !put(&s->triq, tq.data(), tq.size() * sizeof(DevTriQ))))) {
+                 !put(&s->triq, tq.data(), tq.size() * sizeof(DevTriQ)))) ||
+      (x96 && (!put(&s->near4x, nx.data(), nx.size() * sizeof(mcpt::Node96)) ||
+               !put(&s->tri4, t4.data(), t4.size() * sizeof(DevTri)) ||
+               (!n4x.empty() && !put(&s->nodes4x, n4x.data(), n4x.size() * sizeof(DevNode4)))))) {
     mcpt_scene_destroy(s);
     return mcpt::fail(MCPT_ERR_HIP, "scene_upload: device allocation or copy failed");
   }
@@ -2413,6 +2657,11 @@ int mcpt_scene_upload_device(mcpt_ctx *ctx, const mcpt_triangle *tris_dev, int64
     mcpt_scene_destroy(s);
     return rc;
   }
+  rc = node96_device(s, D.n_near4, D.n_nodes4, n_tris, D.root, (hipStream_t)stream);
+  if (rc != MCPT_OK) {
+    mcpt_scene_destroy(s);
+    return rc;
+  }
   if (hipMalloc(&s->mats, n_mats * sizeof(mcpt_material)) != hipSuccess ||
       hipMemcpy(s->mats, mats, n_mats * sizeof(mcpt_material), hipMemcpyHostToDevice) != hipSuccess) {
     mcpt_scene_destroy(s);
@@ -2427,7 +2676,8 @@ int mcpt_scene_upload_device(mcpt_ctx *ctx, const mcpt_triangle *tris_dev, int64
 // A scene's device arrays, copied to the host (introspection: tests compare
 // the two upload paths byte for byte).  which: 0 near4, 1 near4q, 2 nodes4,
 // 3 nodes, 4 tris, 5 triq, 6 int32[4] {stack_depth, stack_depth4, quantized,
-// n_internal}.  *bytes = the array's size; host may be NULL to ask for it.
+// n_internal}, 7 near4x (the 96-B nodes), 8 tri4, 9 nodes4x (0 bytes where the
+// scene has none).  *bytes = the array's size; host may be NULL to ask for it.
 int mcpt_scene_read(const mcpt_scene *s, int32_t which, void *host, int64_t cap, int64_t *bytes) {
   if (!s || !bytes) return mcpt::fail(MCPT_ERR_ARG, "scene_read: bad argument");
   const void *src = nullptr;
@@ -2441,6 +2691,9 @@ int mcpt_scene_read(const mcpt_scene *s, int32_t which, void *host, int64_t cap,
     case 4: src = s->tris, n = s->n_tris * (int64_t)sizeof(DevTri); break;
     case 5: src = s->triq, n = s->triq ? s->n_tris * (int64_t)sizeof(DevTriQ) : 0; break;
     case 6: n = sizeof(meta); break;
+    case 7: src = s->near4x, n = s->near4x ? (int64_t)s->view.n_near4 * (int64_t)sizeof(mcpt::Node96) : 0; break;
+    case 8: src = s->tri4, n = s->tri4 ? 4 * (int64_t)s->view.n_near4 * (int64_t)sizeof(DevTri) : 0; break;
+    case 9: src = s->nodes4x, n = s->nodes4x ? (int64_t)s->view.n_nodes4 * (int64_t)sizeof(DevNode4) : 0; break;
     default: return mcpt::fail(MCPT_ERR_ARG, "scene_read: unknown array");
   }
   *bytes = n;
@@ -2459,7 +2712,8 @@ int mcpt_scene_destroy(mcpt_scene *s) {
   if (!s) return MCPT_OK;
   (void)hipSetDevice(s->device);
   for (void *p : {(void *)s->nodes, (void *)s->nodes4, (void *)s->near4, (void *)s->tris, (void *)s->near4q,
-                  (void *)s->triq, (void *)s->mats, (void *)s->env_map})
+                  (void *)s->triq, (void *)s->mats, (void *)s->env_map, (void *)s->near4x, (void *)s->nodes4x,
+                  (void *)s->tri4})
     if (p) (void)hipFree(p);
   delete s;
   return MCPT_OK;
@@ -2592,7 +2846,7 @@ struct KernelChoice {
   size_t lds;                // dynamic LDS bytes of either
   bool win;                  // the windowed stack
   int per_cu;                // resident workgroups of fn per CU
-  int kind;                  // 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized
+  int kind;                  // 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized, 3 EXACT 96-B nodes
   int depth_entries;         // the whole stack's entries per lane
 };
 
@@ -2608,24 +2862,25 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
   // The stack lives in LDS; when the whole stack would allow fewer resident
   // workgroups than a kStackWindow window does, the windowed kernel runs.
   const bool noprune = p->mode == MCPT_MODE_NOPRUNE;
-  // [environment][jitter][kind: 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized][stats][window][pair][glossy materials]
+  // [environment][jitter][kind: 0 EXACT 128-B nodes, 1 NOPRUNE, 2 EXACT quantized, 3 EXACT 96-B nodes][stats][window][pair][glossy materials]
 #define MCPT_KG(M, ST, W, P, QN, J, E) {(const void *)k_render<M, ST, W, P, QN, false, false, J, E>, \
                                         (const void *)k_render<M, ST, W, P, QN, false, true, J, E>}
 #define MCPT_KR(M, ST, W, QN, J, E) {MCPT_KG(M, ST, W, false, QN, J, E), MCPT_KG(M, ST, W, true, QN, J, E)}
 #define MCPT_KK(M, QN, J, E) {{MCPT_KR(M, false, false, QN, J, E), MCPT_KR(M, false, true, QN, J, E)}, \
                               {MCPT_KR(M, true, false, QN, J, E), MCPT_KR(M, true, true, QN, J, E)}}
-#define MCPT_KJ(J, E) {MCPT_KK(MCPT_MODE_EXACT, false, J, E), MCPT_KK(MCPT_MODE_NOPRUNE, false, J, E), \
-                       MCPT_KK(MCPT_MODE_EXACT, true, J, E)}
+#define MCPT_KJ(J, E) {MCPT_KK(MCPT_MODE_EXACT, kFmt128, J, E), MCPT_KK(MCPT_MODE_NOPRUNE, kFmt128, J, E), \
+                       MCPT_KK(MCPT_MODE_EXACT, kFmtQ, J, E), MCPT_KK(MCPT_MODE_EXACT, kFmt96, J, E)}
   // the leading index: the scene has an environment (the shading forms only; the primary-hit pass has one form)
-  static const void *const kfns[2][2][3][2][2][2][2] = {{MCPT_KJ(false, false), MCPT_KJ(true, false)},
+  static const void *const kfns[2][2][4][2][2][2][2] = {{MCPT_KJ(false, false), MCPT_KJ(true, false)},
                                                         {MCPT_KJ(false, true), MCPT_KJ(true, true)}};
 #undef MCPT_KJ
-  // the primary-hit pass: [kind][window][pair], no stats
+  // the primary-hit pass: [kind][window][pair], no stats (a 96-B launch's pass runs on the 128-B nodes)
 #define MCPT_KP(M, W, QN) {(const void *)k_render<M, false, W, false, QN, true, false>, \
                            (const void *)k_render<M, false, W, true, QN, true, false>}
-  static const void *const kpfns[3][2][2] = {{MCPT_KP(MCPT_MODE_EXACT, false, false), MCPT_KP(MCPT_MODE_EXACT, true, false)},
-                                             {MCPT_KP(MCPT_MODE_NOPRUNE, false, false), MCPT_KP(MCPT_MODE_NOPRUNE, true, false)},
-                                             {MCPT_KP(MCPT_MODE_EXACT, false, true), MCPT_KP(MCPT_MODE_EXACT, true, true)}};
+  static const void *const kpfns[4][2][2] = {{MCPT_KP(MCPT_MODE_EXACT, false, kFmt128), MCPT_KP(MCPT_MODE_EXACT, true, kFmt128)},
+                                             {MCPT_KP(MCPT_MODE_NOPRUNE, false, kFmt128), MCPT_KP(MCPT_MODE_NOPRUNE, true, kFmt128)},
+                                             {MCPT_KP(MCPT_MODE_EXACT, false, kFmtQ), MCPT_KP(MCPT_MODE_EXACT, true, kFmtQ)},
+                                             {MCPT_KP(MCPT_MODE_EXACT, false, kFmt128), MCPT_KP(MCPT_MODE_EXACT, true, kFmt128)}};
 #undef MCPT_KP
 #undef MCPT_KK
 #undef MCPT_KR
@@ -2636,7 +2891,12 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
   // node steps and leaf tests than the saved gathers (C2 +6 %, C3 +11 %;
   // profiles/r02_quant_ab.txt)
   const bool quant = scene->near4q && (T.quantized == 1 || (T.quantized == 0 && scene->near4_bytes > kQuantAutoBytes));
-  const int kind = noprune ? 1 : (quant ? 2 : 0);
+  // 96-B exact nodes (mcpt_node96.h): forced by 3; auto: trees between kNode96AutoMinBytes and
+  // kQuantAutoBytes, where the saved seventh gather was measured to pay
+  const bool x96 = scene->near4x && !quant &&
+                   (T.quantized == 3 || (T.quantized == 0 && scene->near4_bytes > kNode96AutoMinBytes &&
+                                         scene->near4_bytes <= kQuantAutoBytes));
+  const int kind = noprune ? 1 : (quant ? 2 : (x96 ? 3 : 0));
   const int glossy = scene->has_glossy ? 1 : 0;  // the shading instantiation (speed only: same bits)
   const size_t pad = (size_t)std::max(0, T.lds_pad);
   // the search tree's top levels in LDS, stepped where a segment begins
@@ -2887,12 +3147,18 @@ int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera
   HIP_OK(hipEventRecord(ctx->ev0, st));
   int prim_state = 0, launches = 0;
   MCPT_TRY(primary_cache(ctx, scene, cam, p, K, P, st, A, &prim_state));
+  if (K.kind == 3) {  // the render launches search the 96-B tree: its arrays, tri4's indices (k_render, FMT)
+    A.S.near4 = reinterpret_cast<const DevNode4 *>(scene->near4x), A.S.nodes4 = scene->nodes4x, A.S.tris = scene->tri4;
+    A.S.n_tris = 4 * (int64_t)scene->view.n_near4;
+    if (A.S.root_leaf >= 0) A.S.root_leaf = 0;
+  }
   MCPT_TRY(launch_blocks(ctx, p, K, P, st, A, &launches));
   HIP_OK(hipEventRecord(ctx->ev1, st));
   // asynchronous: mcpt_get_stats waits for ev1 and reads the time and counters
   std::memset(&ctx->last, 0, sizeof(ctx->last));
   ctx->last.launches = launches, ctx->last.frames_per_block = P.fpl_head, ctx->last.primary_cache = prim_state;
   ctx->last.stack_window = K.win ? 1 : 0, ctx->last.quantized = K.kind == 2 ? 1 : 0;
+  ctx->last_node_format = K.kind == 2 ? kFmtQ : (K.kind == 3 ? kFmt96 : kFmt128);
   ctx->last.top_levels = A.top_levels, ctx->last.workgroups = (int32_t)(P.grid_wg * kWgWaves);
   ctx->last_pending = true;
   ctx->last_stats = ctx->stats_on || kDebug || kTiming;

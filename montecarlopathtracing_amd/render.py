@@ -45,7 +45,7 @@ class DeviceScene:
     mats) whose tris / nodes are device byte tensors (mcpt_scene_upload_device:
     everything built on the GPU, the same bytes)."""
 
-    ARRAYS = ("near4", "near4q", "nodes4", "nodes", "tris", "triq")
+    ARRAYS = ("near4", "near4q", "nodes4", "nodes", "tris", "triq", "near4x", "tri4", "nodes4x")
 
     def __init__(self, renderer, data):
         self.renderer = renderer
@@ -69,6 +69,7 @@ class DeviceScene:
         """One device array as bytes (mcpt_scene_read; which: a name of ARRAYS
         or "meta" -> int32 {stack_depth, stack_depth4, quantized, n_internal})."""
         k = 6 if which == "meta" else self.ARRAYS.index(which)
+        k += 1 if which != "meta" and k >= 6 else 0  # near4x, tri4, nodes4x: codes 7-9, after the meta record's
         n = ctypes.c_int64()
         L.check(L.lib().mcpt_scene_read(self.handle, k, None, 0, ctypes.byref(n)))
         buf = np.zeros(n.value, np.uint8)
@@ -141,6 +142,10 @@ class Renderer:
         L.check(L.lib().mcpt_get_stats(self.ctx, ctypes.byref(s)))
         out = {f: getattr(s, f) for f, _ in L.Stats._fields_ if f not in ("pad", "pad1")}
         out["phase_ticks"] = list(out["phase_ticks"])
+        if hasattr(L.lib(), "mcpt_get_node_format"):  # 0 128-B, 1 64-B quantized, 2 96-B exact nodes
+            fmt = ctypes.c_int32()
+            L.check(L.lib().mcpt_get_node_format(self.ctx, ctypes.byref(fmt)))
+            out["node_format"] = fmt.value
         return out
 
     def set_pixel_segments(self, counts, iters=None):
@@ -193,7 +198,7 @@ class Renderer:
         """mcpt_set_tuning: k_render launch-plan knobs (leaf_threshold,
         shade_threshold, queue_chunk, block_entries, max_block_frames,
         stack_window 0 auto / 1 window / 2 whole stack, lds_pad, queues, quantized 0 auto / 1
-        the 64-B search-tree nodes / 2 the 128-B ones); speed only,
+        the 64-B search-tree nodes / 2 the 128-B ones / 3 the 96-B exact ones); speed only,
         unnamed knobs take their defaults."""
         t = L.Tuning()
         for k, v in knobs.items():

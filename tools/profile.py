@@ -152,9 +152,11 @@ def summarize(tag):
     shutil.copy(stats_csv, os.path.join(dst, tag + "_kernel_stats.csv"))
     shutil.copy(trace_csv, os.path.join(dst, tag + "_kernel_trace.csv"))
     sched = bench["config"]["schedule"]
-    quant = "true" if bench["config"].get("search_tree_nodes", "").startswith("64") else "false"
+    # the node-format argument: a bool until the 96-B nodes (true: 64-B quantized), then an int
+    # (0 128-B, 1 64-B quantized, 2 96-B exact; bench.py's line says "128-B exact" for both exact formats)
+    quant = "(true|1)" if bench["config"].get("search_tree_nodes", "").startswith("64") else "(false|0|2)"
     # the render instantiation (PRIM = false), not the primary-hit pass (PRIM = true)
-    kname = r"k_render<0, false, (false|true), %s, %s, false, (false|true)(, [a-z0-9]+)?>" % (
+    kname = r"k_render<0, false, (false|true), %s, %s, false, (false|true)(, [a-z0-9]+)*>" % (
         "true" if sched == "paired" else "false", quant)
     trace = [r for r in csv.DictReader(open(trace_csv)) if re.search(kname, r["Kernel_Name"])]
     timed = trace[-1]
