@@ -266,7 +266,9 @@ typedef struct mcpt_tuning {
  * mcpt_generate_rays_jittered added).  A new struct with a new entry point
  * changes neither, so mcpt_denoise_params and mcpt_denoise came in at 5, and
  * so did mcpt_environment with mcpt_scene_set_environment, mcpt_env_eval and
- * mcpt_decode_hdr.
+ * mcpt_decode_hdr, and the vertex-normal entry points (mcpt_vertex_normals,
+ * mcpt_load_obj_normals, mcpt_obj_normals_from_text,
+ * mcpt_scene_set_vertex_normals, mcpt_shading_normals): functions only.
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
 #define MCPT_ABI_VERSION 5
@@ -555,6 +557,88 @@ int mcpt_scene_set_environment(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_envi
  * asynchronous.  With mcpt_generate_rays: the view's background plate.     */
 int mcpt_env_eval(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays_dev, int64_t n,
                   float *out_rgba_dev, void *stream);
+
+/* Opt-in smooth shading from interpolated vertex normals (no reference
+ * counterpart).  The reference, and a scene without vertex
+ * normals, shade every hit with its triangle's packed face normal ng.
+ *
+ * mcpt_vertex_normals generates them on the host from n PACKED triangles
+ * (mcpt_pack_triangles) into vn, n x 3 corners x 3 floats; crease_deg in
+ * [0, 180].  Normative (tests/smooth_ref.py restates it in float64):
+ *   - corners are welded by the exact bits of their position, -0 as +0;
+ *   - corner k of triangle i takes the sum, in double and in ascending
+ *     triangle index, of angle_j * ng_j over the corners of triangles j at the
+ *     same position whose ng_j is bit-equal to ng_i or, for crease_deg > 0, has
+ *     dot(ng_i, ng_j) >= cos(crease) (the dot in double); angle_j = triangle
+ *     j's interior angle there, atan2(|e x f|, e . f) of its two edges;
+ *   - the sum is normalised in double and rounded to float once;
+ *   - a triangle whose ng is not finite or whose length is not within 1e-3 of
+ *     1 (degenerate) contributes nowhere and keeps ng at its corners;
+ *   - a corner whose contributing normals are all bit-equal to ng_i, or whose
+ *     sum is shorter than 1e-12, takes ng_i bit for bit: a cube, and any mesh
+ *     at crease 0, comes out exactly flat.
+ * An oppositely wound neighbour has dot ~ -1 and is excluded like any crease.
+ * The weld is a sort of the corners by position: O(n log n).  A vertex shared
+ * by m corners costs O(m) when all their face normals lie within half the
+ * crease angle of their mean (a pole, a flat fan: every pair is then inside
+ * the crease and every corner takes the one sum, the same value the pairwise
+ * rule gives), else m^2 pair tests; MCPT_ERR_LIMIT when such a vertex has
+ * more than 65536 corners.
+ *
+ * mcpt_load_obj_normals reads authored normals: the `vn` records and the
+ * third index of "v/vt/vn" and "v//vn" corners (negative indices count back
+ * from the records read so far), with mcpt_load_obj's fan triangulation and
+ * triangle order.  has[i] = 1 when all three corners of triangle i name a vn
+ * record of finite, non-zero length; vn[9 i ..] then holds them normalised in
+ * double, else zeros.  vn and has NULL: *n_tris = the count only; otherwise
+ * *n_tris is the buffers' capacity in triangles on entry.  MCPT_ERR_PARSE: a
+ * vn index past the file's records or before the first, a face index of 0.
+ * mcpt_obj_normals_from_text is the same parser on `len` bytes in memory
+ * (it reads exactly those bytes).
+ *
+ * mcpt_scene_set_vertex_normals(ctx, scene, vn): vn = n_tris x 9 floats on
+ * the host in the upload's triangle order, n_tris the scene's count; every
+ * normal finite with length within 1e-3 of 1, except in a triangle whose
+ * three normals are bit-equal to its packed normal (flat: never
+ * interpolated).  Uploads 48 B per triangle (two copies, 48 B per triangle
+ * and 192 B per search-tree node, in a scene that has the 96-B nodes),
+ * replacing the scene's previous ones; vn NULL clears them (the bits of a
+ * scene that never had any).  It waits for work enqueued on the scene's GPU
+ * before it frees a previous array, and drops the context's primary-hit
+ * cache (its records hold shading normals).  MCPT_ERR_ARG leaves the scene
+ * as it was.  mcpt_scene_destroy frees the arrays.
+ *
+ * The lookup, for a hit at point pt of a ray with direction d on triangle T
+ * with rows v0, e1 = v1 - v0, e2 = v2 - v0 and vertex normals n0, n1, n2
+ * (fp32 on the device, csrc/mcpt_smooth.h; float64 in tests/smooth_ref.py):
+ *   ngf = ng, negated when dot(d, ng) > 0 (the reference's flip,
+ *         intersect.cl:23-25);
+ *   a triangle whose vertex normals are all bit-equal to ng gives ngf, the
+ *   bits a scene without vertex normals gives;
+ *   w = pt - v0, d11 = e1.e1, d12 = e1.e2, d22 = e2.e2, w1 = w.e1, w2 = w.e2,
+ *   den = d11 d22 - d12^2, b1 = clamp((d22 w1 - d12 w2) / den, 0, 1),
+ *   b2 = clamp((d11 w2 - d12 w1) / den, 0, 1), b0 = max(0, 1 - b1 - b2);
+ *   ns = normalize(b0 n0 + b1 n1 + b2 n2), negated when dot(ns, ngf) < 0;
+ *   ngf instead when den or |ns|^2 is zero or not finite.
+ * The result replaces the flipped face normal wherever a hit is shaded:
+ * mcpt_render_frames (every material's in.nrm), the primary-hit records,
+ * mcpt_intersect's mcpt_hit.normal (so mcpt_shade and mcpt_denoise's guide
+ * follow).  No random number is drawn for it and a sampled direction below
+ * the geometric surface is traced as sampled.
+ * mcpt_render_frames with vertex normals set supports MCPT_MODE_EXACT and
+ * MCPT_MODE_NOPRUNE alike.
+ *
+ * mcpt_shading_normals evaluates the lookup for n queries on the device:
+ * tri_ids_dev int32 triangle indices (upload order), points_dev and dirs_dev
+ * n float4 (xyz used), out_dev n float4 (w = +-0).  MCPT_ERR_ARG when the
+ * scene has no vertex normals; an index outside the scene's triangles gives
+ * zeros.  Stream-ordered and asynchronous.                                 */
+int mcpt_vertex_normals(const mcpt_triangle *packed_tris, int64_t n, double crease_deg, float *vn);
+int mcpt_load_obj_normals(const char *directory, const char *objname, float *vn, uint8_t *has, int64_t *n_tris);
+int mcpt_obj_normals_from_text(const char *text, int64_t len, float *vn, uint8_t *has, int64_t *n_tris);
+int mcpt_scene_set_vertex_normals(mcpt_ctx *ctx, mcpt_scene *scene, const float *vn);
+int mcpt_shading_normals(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *tri_ids_dev, const float *points_dev,
+                         const float *dirs_dev, int64_t n, float *out_dev, void *stream);
 
 /* Counters of the last render call (segments etc. need stats enabled);
  * waits for that call's work to finish.                                   */

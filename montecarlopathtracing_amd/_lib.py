@@ -102,6 +102,11 @@ SIGNATURES = {
     "mcpt_decode_hdr": (_I32, [_P, _I64, _P, _P, _P, _I64]),
     "mcpt_scene_set_environment": (_I32, [_P, _P, _P]),
     "mcpt_env_eval": (_I32, [_P, _P, _P, _I64, _P, _P]),
+    "mcpt_vertex_normals": (_I32, [_P, _I64, _D, _P]),
+    "mcpt_load_obj_normals": (_I32, [_S, _S, _P, _P, _P]),
+    "mcpt_obj_normals_from_text": (_I32, [_P, _I64, _P, _P, _P]),
+    "mcpt_scene_set_vertex_normals": (_I32, [_P, _P, _P]),
+    "mcpt_shading_normals": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),
     "mcpt_ctx_create": (_I32, [_I32, _P]),
     "mcpt_ctx_destroy": (_I32, [_P]),
     "mcpt_device_count": (_I32, [_P]),

@@ -26,6 +26,13 @@ lights the rays that leave the scene with a constant or a lat-long .hdr map
 instead of the reference's black (Renderer.set_environment).  The denoise
 pass needs nothing for it: a pixel whose first hit is a miss passes through,
 so the sky stays sharp.
+
+Extension: "smooth": true | <crease degrees> (App(..., smooth=...), --smooth
+[DEG]) shades every hit with the normal interpolated from vertex normals (the
+OBJ file's `vn` records where it has them, generated ones elsewhere; creases
+sharper than the angle, default 40 degrees, stay creases) instead of the
+triangle's face normal (Renderer.set_vertex_normals).  The denoise pass's
+guide follows: first_hits returns the shading normals.
 """
 import os
 
@@ -71,9 +78,23 @@ def apply_environment(renderer, scene, env, cfg, root):
     renderer.set_environment(scene, scale=env["scale"], map=texels, rotate=env["rotate"])
 
 
+def apply_smooth(renderer, scene, crease, cfg, root):
+    """Set a config entry's smooth shading (config.parse_smooth's crease angle,
+    or None: leave the face normals) on an uploaded scene: the OBJ file's
+    authored normals where a triangle has them, generated ones elsewhere.
+    App.init and every rank of the multi-GPU CLI go through this."""
+    if crease is None:
+        return
+    directory = os.path.join(root, cfg.GETDIRECTORY())
+    if not directory.endswith("/"):
+        directory += "/"
+    authored = S.load_obj_normals(directory, cfg.GETOBJNAME())
+    renderer.set_vertex_normals(scene, S.smooth_normals(scene.data.tris, crease, authored))
+
+
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
-                 material_override=None, jitter=None, denoise=None, environment=None):
+                 material_override=None, jitter=None, denoise=None, environment=None, smooth=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -90,6 +111,8 @@ class App:
         self.denoise = self.cfg.DENOISE() if denoise is None else bool(denoise)  # None: the entry's "denoise" key
         # None: the entry's "environment" key; else that key's value ({"color": ..} or {"map": ..})
         self.environment = self.cfg.ENVIRONMENT() if environment is None else C.parse_environment(environment)
+        # None: the entry's "smooth" key; else that key's value (True / False / crease degrees)
+        self.smooth = self.cfg.SMOOTH() if smooth is None else C.parse_smooth(smooth)
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -109,6 +132,7 @@ class App:
         self.renderer = R.Renderer(self.device)
         self.scene = self.renderer.upload(self.data)
         apply_environment(self.renderer, self.scene, self.environment, self.cfg, self.root)
+        apply_smooth(self.renderer, self.scene, self.smooth, self.cfg, self.root)
         self.state = self.renderer.new_state(self.w, self.h, self.seeds)
         self._init = True
 

@@ -55,6 +55,25 @@ def _env_rgb(v, what):
     return rgb
 
 
+DEFAULT_CREASE = 40.0  # degrees: what "smooth": true means.  A quality choice, not a measured optimum: edges
+# sharper than this (a box's 90, a faceted gem's) stay edges, tessellated curves (an icosphere's ~20-37) blend
+
+
+def parse_smooth(v):
+    """The "smooth" extension key of a config entry -> the crease angle in
+    degrees, or None (false: face normals).  true is DEFAULT_CREASE; a number
+    is the angle, in [0, 180]."""
+    if v is False:
+        return None
+    if v is True:
+        return DEFAULT_CREASE
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError('config "smooth" must be true, false or a crease angle in degrees, got %r' % (v,))
+    if not (math.isfinite(v) and 0.0 <= v <= 180.0):
+        raise ValueError('config "smooth": the crease angle must lie in [0, 180] degrees, got %r' % (v,))
+    return float(v)
+
+
 def parse_environment(e):
     """The "environment" extension key of a config entry ->
     {"scale": (r, g, b), "map": path or None, "rotate": degrees}.
@@ -112,6 +131,9 @@ class Config:
         # "environment": what a ray that leaves the scene picks up
         # (Renderer.set_environment); None: the reference's black
         self.environment = parse_environment(c["environment"]) if "environment" in c else None
+        # "smooth": true | <crease degrees>: shade with interpolated vertex normals
+        # (Renderer.set_vertex_normals); None: the reference's face normals
+        self.smooth = parse_smooth(c["smooth"]) if "smooth" in c else None
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -155,3 +177,4 @@ class Config:
     def JITTER(self): return self.jitter  # extension: sub-pixel jitter of the render path
     def DENOISE(self): return self.denoise  # extension: the denoise post-pass
     def ENVIRONMENT(self): return self.environment  # extension: parse_environment's dict, or None
+    def SMOOTH(self): return self.smooth  # extension: smooth shading's crease angle in degrees, or None

@@ -819,3 +819,217 @@ extern "C" int mcpt_write_hdr(const char *path, int32_t width, int32_t height, c
   if (wr != bytes.size()) return fail(MCPT_ERR_IO, "write_hdr: short write");
   return MCPT_OK;
 }
+
+// ---------------------------------------------------------- vertex normals
+// Smooth shading's host half (opt-in, no reference counterpart; the normative
+// text is in include/mcpt_hip.h): vertex normals generated from the packed
+// triangles, and authored ones read from an OBJ file's `vn` records.
+namespace {
+
+inline uint32_t weld_bits(float f) {  // a position component's bits, -0 as +0
+  uint32_t u;
+  std::memcpy(&u, &f, 4);
+  return u == 0x80000000u ? 0u : u;
+}
+struct Corner {
+  uint32_t key[3];
+  uint32_t id;  // 3 * triangle + corner
+};
+constexpr int64_t kMaxPairwiseValence = 65536;  // mcpt_vertex_normals' pairwise path (include/mcpt_hip.h)
+inline bool corner_less(const Corner &a, const Corner &b) {
+  for (int k = 0; k < 3; ++k)
+    if (a.key[k] != b.key[k]) return a.key[k] < b.key[k];
+  return a.id < b.id;  // ascending triangle index inside a welded vertex
+}
+
+// one OBJ corner "v", "v/vt", "v//vn" or "v/vt/vn": the first and third integer (0: absent or malformed)
+void corner_indices(const char *p, const char *e, long *v, long *vn) {
+  long f[3] = {0, 0, 0};
+  for (int k = 0; k < 3 && p < e; ++k) {
+    const char *s = p;
+    while (p < e && *p != '/') ++p;
+    if (p - s > 0 && p - s < 24) f[k] = std::strtol(std::string(s, p).c_str(), nullptr, 10);
+    if (p < e) ++p;  // the slash
+  }
+  *v = f[0], *vn = f[2];
+}
+
+}  // namespace
+
+extern "C" int mcpt_vertex_normals(const mcpt_triangle *tris, int64_t n, double crease_deg, float *vn) {
+  if (n < 0 || (n > 0 && (!tris || !vn))) return fail(MCPT_ERR_ARG, "vertex_normals: bad argument");
+  if (!(crease_deg >= 0.0 && crease_deg <= 180.0)) return fail(MCPT_ERR_ARG, "vertex_normals: crease outside [0, 180] degrees");
+  if (n > (int64_t)0x3FFFFFFF) return fail(MCPT_ERR_LIMIT, "vertex_normals: too many triangles");
+  const double cosc = std::cos(crease_deg * (3.14159265358979323846 / 180.0));
+  // a face normal that is not finite or not unit: the triangle is degenerate, joins no vertex and stays flat
+  std::vector<uint8_t> valid((size_t)n);
+  for (int64_t i = 0; i < n; ++i) {
+    const float *g = tris[i].normal;
+    const double l2 = (double)g[0] * g[0] + (double)g[1] * g[1] + (double)g[2] * g[2];
+    valid[(size_t)i] = std::isfinite(l2) && std::fabs(std::sqrt(l2) - 1.0) <= 1e-3;
+    for (int k = 0; k < 3; ++k) std::memcpy(vn + 9 * i + 3 * k, g, 12);
+  }
+  // weld: corners sorted by their position's bits; a run of equal keys is one vertex
+  std::vector<Corner> cs;
+  cs.reserve((size_t)n * 3);
+  for (int64_t i = 0; i < n; ++i) {
+    if (!valid[(size_t)i]) continue;
+    for (int k = 0; k < 3; ++k) {
+      const float *p = tris[i].v[k];
+      cs.push_back(Corner{{weld_bits(p[0]), weld_bits(p[1]), weld_bits(p[2])}, (uint32_t)(3 * i + k)});
+    }
+  }
+  std::sort(cs.begin(), cs.end(), corner_less);
+  std::vector<double> wn;  // per corner of the run: angle * ng
+  for (size_t lo = 0; lo < cs.size();) {
+    size_t hi = lo + 1;
+    while (hi < cs.size() && std::memcmp(cs[hi].key, cs[lo].key, 12) == 0) ++hi;
+    wn.resize(3 * (hi - lo));
+    for (size_t a = lo; a < hi; ++a) {  // triangle j's interior angle at this corner, times its face normal
+      const mcpt_triangle &t = tris[cs[a].id / 3];
+      const int k = (int)(cs[a].id % 3);
+      const float *p = t.v[k], *q = t.v[(k + 1) % 3], *r = t.v[(k + 2) % 3];
+      const double e[3] = {(double)q[0] - p[0], (double)q[1] - p[1], (double)q[2] - p[2]};
+      const double f[3] = {(double)r[0] - p[0], (double)r[1] - p[1], (double)r[2] - p[2]};
+      const double cx = e[1] * f[2] - e[2] * f[1], cy = e[2] * f[0] - e[0] * f[2], cz = e[0] * f[1] - e[1] * f[0];
+      const double ang = std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), e[0] * f[0] + e[1] * f[1] + e[2] * f[2]);
+      for (int c = 0; c < 3; ++c) wn[3 * (a - lo) + c] = ang * (double)t.normal[c];
+    }
+    // A vertex of many corners (a pole, a fan's apex) whose normals all sit in one narrow cone: every pair
+    // is then inside the crease, every corner's sum is the whole run's, in the same order: one sum, O(m).
+    // Sufficient, not necessary (angles to the run's mean direction, the triangle inequality, and margins
+    // far above the rounding of the dots); a run that fails it takes the pairwise loop below.
+    const size_t m = hi - lo;
+    bool one_cone = crease_deg >= 1.0 && crease_deg <= 179.0, identical = true;
+    double sum[3] = {0.0, 0.0, 0.0};
+    {
+      const float *g0 = tris[cs[lo].id / 3].normal;
+      double c[3] = {0.0, 0.0, 0.0};
+      for (size_t b = lo; b < hi; ++b) {
+        const float *gj = tris[cs[b].id / 3].normal;
+        identical = identical && std::memcmp(g0, gj, 12) == 0;
+        for (int k = 0; k < 3; ++k) c[k] += gj[k], sum[k] += wn[3 * (b - lo) + k];
+      }
+      const double cl = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+      const double half = std::cos(0.5 * crease_deg * (3.14159265358979323846 / 180.0) - 1e-4);
+      one_cone = one_cone && cl > 0.5 * (double)m;
+      for (size_t b = lo; one_cone && b < hi; ++b) {
+        const float *gj = tris[cs[b].id / 3].normal;
+        const double l2 = (double)gj[0] * gj[0] + (double)gj[1] * gj[1] + (double)gj[2] * gj[2];
+        const double d = (c[0] * gj[0] + c[1] * gj[1] + c[2] * gj[2]) / cl;
+        one_cone = std::fabs(l2 - 1.0) <= 2e-6 && d >= half * (1.0 + 2e-6);
+      }
+    }
+    if (one_cone) {
+      const double len = std::sqrt(sum[0] * sum[0] + sum[1] * sum[1] + sum[2] * sum[2]);
+      if (!identical && len >= 1e-12)
+        for (size_t a = lo; a < hi; ++a)
+          for (int k = 0; k < 3; ++k) vn[3 * (size_t)cs[a].id + k] = (float)(sum[k] / len);
+      lo = hi;
+      continue;
+    }
+    // the general case costs m^2 pair tests: bounded, so that no input runs for hours
+    if (m > (size_t)kMaxPairwiseValence)
+      return fail(MCPT_ERR_LIMIT, "vertex_normals: a vertex is shared by more than 65536 corners whose face normals "
+                                  "spread beyond half the crease angle");
+    for (size_t a = lo; a < hi; ++a) {
+      const float *gi = tris[cs[a].id / 3].normal;
+      double s[3] = {0.0, 0.0, 0.0};
+      bool all_equal = true;
+      for (size_t b = lo; b < hi; ++b) {
+        const float *gj = tris[cs[b].id / 3].normal;
+        const bool same = std::memcmp(gi, gj, 12) == 0;
+        const double dot = (double)gi[0] * gj[0] + (double)gi[1] * gj[1] + (double)gi[2] * gj[2];
+        if (!(same || (crease_deg > 0.0 && dot >= cosc))) continue;
+        all_equal = all_equal && same;
+        for (int c = 0; c < 3; ++c) s[c] += wn[3 * (b - lo) + c];
+      }
+      const double len = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+      if (all_equal || !(len >= 1e-12)) continue;  // stays the face normal, bit for bit
+      float *out = vn + 3 * (size_t)cs[a].id;
+      for (int c = 0; c < 3; ++c) out[c] = (float)(s[c] / len);
+    }
+    lo = hi;
+  }
+  return MCPT_OK;
+}
+
+extern "C" int mcpt_obj_normals_from_text(const char *text, int64_t len, float *vn, uint8_t *has, int64_t *n_tris) {
+  if (!n_tris || len < 0 || (len > 0 && !text)) return fail(MCPT_ERR_ARG, "obj_normals: bad argument");
+  std::vector<double> normals;  // the vn records, as parsed
+  struct FaceN {
+    long n[3];  // 0-based vn index per corner, -1: none
+  };
+  std::vector<FaceN> faces;
+  std::vector<long> poly;
+  const char *p = text, *end = text + len;
+  while (p < end) {
+    const char *eol = (const char *)std::memchr(p, '\n', end - p);
+    if (!eol) eol = end;
+    const char *q = p;
+    while (q < eol && (*q == ' ' || *q == '\t')) ++q;
+    if (q + 2 < eol && q[0] == 'v' && q[1] == 'n' && (q[2] == ' ' || q[2] == '\t')) {
+      q += 3;
+      for (int k = 0; k < 3; ++k) {
+        Tok t = next_token(q, eol);
+        double v = 0.0;
+        parse_number(t.p, t.e, &v);
+        normals.push_back(v);
+      }
+    } else if (q + 1 < eol && q[0] == 'f' && (q[1] == ' ' || q[1] == '\t')) {
+      q += 2;
+      poly.clear();
+      const long nvn = (long)(normals.size() / 3);
+      for (;;) {
+        Tok t = next_token(q, eol);
+        if (t.p == t.e) break;
+        long v, n;
+        corner_indices(t.p, t.e, &v, &n);
+        if (v == 0) return fail(MCPT_ERR_PARSE, "obj_normals: bad face index");  // as mcpt_load_obj
+        if (n < 0 && nvn + n < 0) return fail(MCPT_ERR_PARSE, "obj_normals: vn index out of range");
+        poly.push_back(n > 0 ? n - 1 : (n < 0 ? nvn + n : -1));
+      }
+      if (poly.size() < 3) {
+        p = eol + 1;
+        continue;
+      }
+      for (size_t k = 1; k + 1 < poly.size(); ++k) faces.push_back(FaceN{{poly[0], poly[k], poly[k + 1]}});
+    }
+    p = eol + 1;
+  }
+  const long nvn = (long)(normals.size() / 3);
+  for (const FaceN &f : faces)
+    for (int k = 0; k < 3; ++k)
+      if (f.n[k] >= nvn) return fail(MCPT_ERR_PARSE, "obj_normals: vn index out of range");
+  if (vn || has) {
+    if (!vn || !has) return fail(MCPT_ERR_ARG, "obj_normals: vn and has come together");
+    if (*n_tris < (int64_t)faces.size()) return fail(MCPT_ERR_ARG, "obj_normals: buffers too small");
+    for (size_t i = 0; i < faces.size(); ++i) {
+      bool ok = true;
+      float out[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      for (int k = 0; k < 3 && ok; ++k) {
+        if (faces[i].n[k] < 0) {
+          ok = false;
+          break;
+        }
+        const double *v = &normals[3 * (size_t)faces[i].n[k]];
+        const double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        ok = std::isfinite(l) && l > 0.0;
+        for (int c = 0; c < 3 && ok; ++c) out[3 * k + c] = (float)(v[c] / l);
+      }
+      if (!ok) std::memset(out, 0, sizeof out);
+      std::memcpy(vn + 9 * i, out, sizeof out);
+      has[i] = ok ? 1 : 0;
+    }
+  }
+  *n_tris = (int64_t)faces.size();
+  return MCPT_OK;
+}
+
+extern "C" int mcpt_load_obj_normals(const char *directory, const char *objname, float *vn, uint8_t *has,
+                                     int64_t *n_tris) {
+  if (!directory || !objname || !n_tris) return fail(MCPT_ERR_ARG, "load_obj_normals: null argument");
+  std::string dir(directory), text;
+  if (!read_file(dir + objname, &text)) return fail(MCPT_ERR_IO, "load_obj_normals: cannot read " + dir + objname);
+  return mcpt_obj_normals_from_text(text.data(), (int64_t)text.size(), vn, has, n_tris);
+}

@@ -493,6 +493,42 @@ class Renderer:
         L.check(L.lib().mcpt_env_eval(self.ctx, scene.handle, L.ptr(rays), n, L.ptr(out), _stream()))
         return out
 
+    # ----------------------------------------------- smooth shading (opt-in)
+    def set_vertex_normals(self, scene, vn):
+        """mcpt_scene_set_vertex_normals: hits on `scene` are shaded with the
+        normal interpolated from `vn`, (n_tris, 3, 3) float32 unit normals in
+        the upload's triangle order (scene.vertex_normals, load_obj_normals or
+        smooth_normals), instead of the face normal.  Replaces previous ones and
+        drops the primary-hit cache."""
+        v = np.ascontiguousarray(vn, np.float32)
+        n = len(scene.data.tris) if hasattr(scene.data, "tris") else scene.data[0].numel() // L.TRIANGLE.itemsize
+        if v.size != n * 9:
+            raise ValueError("set_vertex_normals: %d triangles need (n, 3, 3) normals, got %r" % (n, v.shape))
+        L.check(L.lib().mcpt_scene_set_vertex_normals(self.ctx, scene.handle, L.ptr(v)))
+
+    def clear_vertex_normals(self, scene):
+        """Back to the face normals (the bits of a scene that never had vertex normals)."""
+        L.check(L.lib().mcpt_scene_set_vertex_normals(self.ctx, scene.handle, None))
+
+    def shading_normals(self, scene, tri_ids, points, dirs):
+        """mcpt_shading_normals: the shading normal of (triangle, hit point, ray
+        direction) queries on a scene with vertex normals: a float32 (n, 4)
+        device tensor.  tri_ids: n int32; points, dirs: (n, 3) or (n, 4)."""
+        ids = torch.as_tensor(np.ascontiguousarray(tri_ids, np.int32)).to(self.device)
+        n = ids.numel()
+
+        def quad(a):
+            a = np.asarray(a, np.float32).reshape(n, -1)
+            q = np.zeros((n, 4), np.float32)
+            q[:, :a.shape[1]] = a
+            return torch.from_numpy(q).to(self.device)
+        p, d = quad(points), quad(dirs)
+        out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        L.check(L.lib().mcpt_shading_normals(self.ctx, scene.handle, L.ptr(ids), L.ptr(p), L.ptr(d), n, L.ptr(out),
+                                             _stream()))
+        torch.cuda.current_stream().synchronize()  # (the inputs above are temporaries)
+        return out
+
     # ------------------------------------------------------ denoise (opt-in)
     def first_hits(self, scene, camera, width, height, mode=L.MODE_EXACT):
         """Every pixel's first hit (W*H Hit records, device bytes): generate_rays

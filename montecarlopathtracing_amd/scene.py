@@ -57,6 +57,46 @@ def pack_triangles(tris, mat_index):
     return t
 
 
+from .config import DEFAULT_CREASE  # degrees; a quality choice: creases sharper than this stay creases
+
+
+def vertex_normals(tris, crease=DEFAULT_CREASE):
+    """Vertex normals for smooth shading, generated from PACKED triangles
+    (mcpt_vertex_normals, include/mcpt_hip.h): (n, 3, 3) float32, corner k of
+    triangle i the angle-weighted mean of the face normals around its welded
+    vertex that lie within `crease` degrees of triangle i's."""
+    t = np.ascontiguousarray(tris)
+    out = np.zeros((len(t), 3, 3), np.float32)
+    L.check(L.lib().mcpt_vertex_normals(L.ptr(t), len(t), float(crease), L.ptr(out)))
+    return out
+
+
+def load_obj_normals(directory, objname):
+    """Authored normals of an OBJ file (its `vn` records): (vn[n, 3, 3] float32,
+    has[n] bool) in load_object's triangle order; has[i] is False where a
+    corner of triangle i names no usable normal (vn[i] is zero there)."""
+    lib = L.lib()
+    nt = ctypes.c_int64(0)
+    d, o = directory.encode(), objname.encode()
+    L.check(lib.mcpt_load_obj_normals(d, o, None, None, ctypes.byref(nt)))
+    vn = np.zeros((nt.value, 3, 3), np.float32)
+    has = np.zeros(nt.value, np.uint8)
+    L.check(lib.mcpt_load_obj_normals(d, o, L.ptr(vn), L.ptr(has), ctypes.byref(nt)))
+    return vn, has.astype(bool)
+
+
+def smooth_normals(tris, crease=DEFAULT_CREASE, authored=None):
+    """What a smooth scene uploads: authored normals (load_obj_normals' pair)
+    where a triangle has them, generated ones elsewhere."""
+    vn = vertex_normals(tris, crease)
+    if authored is not None:
+        avn, has = authored
+        if len(avn) != len(vn):
+            raise ValueError("authored normals of another mesh")
+        vn[has] = avn[has]
+    return vn
+
+
 def build_hlbvh(tris):
     """HLBVH<CPU>: 2n-1 BVHNode records (root 0, leaves at [n-1, 2n-2])."""
     n = len(tris)

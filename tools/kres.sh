@@ -1,6 +1,7 @@
 #!/bin/bash
 # Register / scratch / occupancy of every k_render instantiation (compile-time, no GPU):
 #   bash tools/kres.sh [extra hipcc flags]
+#   bash tools/kres.sh -DMCPT_SMOOTH_TU     the smooth-shading (N) forms' translation unit instead
 cd "$(dirname "$0")/../montecarlopathtracing_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on \
   -fno-hip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function "$@" -c mcpt_device.hip -o /tmp/kres.o \
