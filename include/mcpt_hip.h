@@ -269,6 +269,9 @@ typedef struct mcpt_tuning {
  * mcpt_decode_hdr, and the vertex-normal entry points (mcpt_vertex_normals,
  * mcpt_load_obj_normals, mcpt_obj_normals_from_text,
  * mcpt_scene_set_vertex_normals, mcpt_shading_normals): functions only.
+ * The texture entry points (mcpt_load_obj_uvs, mcpt_obj_uvs_from_text,
+ * mcpt_load_mtl_maps, mcpt_mtl_maps_from_text, mcpt_scene_set_textures with
+ * its own mcpt_textures, mcpt_texture_eval) came in at 5 likewise.
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
 #define MCPT_ABI_VERSION 5
@@ -639,6 +642,97 @@ int mcpt_obj_normals_from_text(const char *text, int64_t len, float *vn, uint8_t
 int mcpt_scene_set_vertex_normals(mcpt_ctx *ctx, mcpt_scene *scene, const float *vn);
 int mcpt_shading_normals(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *tri_ids_dev, const float *points_dev,
                          const float *dirs_dev, int64_t n, float *out_dev, void *stream);
+
+/* Opt-in diffuse texture maps (OBJ `vt`, MTL `map_Kd`; no reference
+ * counterpart).  The reference, and a scene without textures,
+ * shade the diffuse lobe with the material's kd alone.
+ *
+ * Normative (fp32 on the device, csrc/mcpt_texture.h; float64 in
+ * tests/texture_ref.py).  A scene has a pool of textures, each W x H linear
+ * RGB float texels, row 0 the top, every texel finite and >= 0.  Each triangle
+ * has three UV pairs and a texture index, or -1: no texture.  For a hit at
+ * point pt on triangle T with rows v0, e1 = v1 - v0, e2 = v2 - v0:
+ *   b0, b1, b2: the barycentrics of the smooth lookup above (the same rows,
+ *     fmas, one v_rcp_f32 and clamps); den zero or not finite: b1 = b2 = 0;
+ *   u = b0 u0 + b1 u1 + b2 u2 and v likewise, as fma chains
+ *     fma(b2, u2, fma(b1, u1, b0 u0));
+ *   u' = u - floor(u), v' = v - floor(v): every texture repeats on both axes;
+ *   x = u' W - 0.5, y = (1 - v') H - 0.5 (OBJ's v axis points up), each one
+ *     fma; i0 = floor(x), j0 = floor(y), fx = x - i0, fy = y - j0;
+ *   bilinear over columns i0, i0 + 1 and rows j0, j0 + 1, BOTH taken modulo W
+ *     and H, with the environment map's weights and fma order
+ *     (w00 = (1-fx)(1-fy), w10 = fx (1-fy), w01 = (1-fx) fy, w11 = fx fy;
+ *     fma(w11, t11, fma(w01, t01, fma(w10, t10, w00 t00)))); a channel whose
+ *     four texels are equal is that value exactly (the four fp32 weights sum
+ *     to 1 only within an ulp, and a texture of ones must give 1.0f);
+ *   Tex = (r, g, b, 1); an untextured triangle gives (1, 1, 1, 1) after one
+ *     16-B gather.
+ * Shading: kd is replaced by kd * Tex, one multiply per lane, wherever the
+ * diffuse lobe of MCPT_DIFFUSE and of MCPT_GLOSSY reads kd.  ks, a light's
+ * ka, glass and the environment are untouched; no random number is drawn;
+ * x * 1.0f is exact, so a texture of ones, or none, gives the untextured bits.
+ * There are no mip levels: minification aliasing at primary hits averages out
+ * only with jitter.
+ *
+ * mcpt_load_obj_uvs reads the `vt` records and the second index of "v/vt" and
+ * "v/vt/vn" corners (negative indices count back from the records read so
+ * far) with mcpt_load_obj's fan triangulation and triangle order: uv[6 i ..] =
+ * (u0, v0, u1, v1, u2, v2), has[i] = 1 when all three corners of triangle i
+ * name a finite vt, else zeros.  uv and has NULL: *n_tris = the count only;
+ * otherwise *n_tris is the buffers' capacity in triangles on entry.
+ * MCPT_ERR_PARSE: a vt index of 0, or one outside the file's records.
+ * mcpt_obj_uvs_from_text is the same parser on `len` bytes in memory.
+ *
+ * mcpt_load_mtl_maps returns each material's map_Kd file name in
+ * mcpt_load_obj's material order (the `newmtl` records of the OBJ file's
+ * mtllib, in order): '\0'-terminated names back to back, an empty name for a
+ * material without a map.  Options before the name (-s, -o, -clamp, -bm, ...)
+ * are skipped, not honoured; backslashes become slashes.  Two calls: names
+ * NULL gives *n_bytes and *n_materials; otherwise *n_bytes is the buffer's
+ * capacity on entry.  mcpt_mtl_maps_from_text is the same on MTL text.
+ *
+ * mcpt_scene_set_textures(ctx, scene, t): host uv (n_tris x 6) and tri_tex
+ * (n_tris) in the upload's triangle order, n_textures images {rgb, width,
+ * height} of width * height * 3 floats.  Validated first: UVs of textured
+ * triangles finite with |uv| <= 2^20, indices in [-1, n_textures), texels
+ * finite and >= 0, sides in 1..16384, at most 2^27 texels in all;
+ * MCPT_ERR_ARG leaves the scene as it was.  Uploads float4 texels in one pool
+ * and a 32-B record per triangle (a second copy per search-tree slot in a
+ * scene that has the 96-B nodes); t NULL clears the textures.  It waits for
+ * work enqueued on the scene's GPU before it frees previous arrays and drops
+ * the context's primary-hit cache.  mcpt_scene_destroy frees the arrays.
+ *
+ * With textures set: mcpt_render_frames runs k_render's textured forms (both
+ * modes; with or without vertex normals); its primary-hit cache holds each
+ * pixel's texture factor beside the hit (16 B per pixel more), the same bits
+ * with mcpt_tuning.primary_cache off, auto or always;
+ * mcpt_shade multiplies kd by the factor at the hit's triangle_id and point;
+ * mcpt_intersect reports the closest hit's triangle in triangle_id in
+ * MCPT_MODE_NOPRUNE too (without textures: the reference's last accepted
+ * triangle), so that the chain of wavefront kernels looks the texel up on the
+ * triangle the point lies on.
+ *
+ * mcpt_texture_eval evaluates the factor for n queries on the device:
+ * tri_ids_dev int32 triangle indices (upload order), points_dev n float4 (xyz
+ * used), out_dev n float4.  MCPT_ERR_ARG when the scene has no textures; an
+ * index outside the scene's triangles gives zeros.  Stream-ordered.       */
+typedef struct mcpt_texture_image {
+  const float *rgb; /* width * height * 3, row 0 the top */
+  int32_t width, height;
+} mcpt_texture_image;
+typedef struct mcpt_textures {
+  const float *uv;          /* n_tris x 6 */
+  const int32_t *tri_tex;   /* n_tris, -1: no texture */
+  int32_t n_textures;
+  const mcpt_texture_image *images;
+} mcpt_textures;
+int mcpt_load_obj_uvs(const char *directory, const char *objname, float *uv, uint8_t *has, int64_t *n_tris);
+int mcpt_obj_uvs_from_text(const char *text, int64_t len, float *uv, uint8_t *has, int64_t *n_tris);
+int mcpt_load_mtl_maps(const char *directory, const char *objname, char *names, int64_t *n_bytes, int64_t *n_materials);
+int mcpt_mtl_maps_from_text(const char *text, int64_t len, char *names, int64_t *n_bytes, int64_t *n_materials);
+int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_textures *textures);
+int mcpt_texture_eval(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *tri_ids_dev, const float *points_dev,
+                      int64_t n, float *out_dev, void *stream);
 
 /* Counters of the last render call (segments etc. need stats enabled);
  * waits for that call's work to finish.                                   */

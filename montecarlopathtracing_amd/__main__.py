@@ -3,6 +3,7 @@ or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
         [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]] [--smooth [DEG]]
+        [--textures]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -36,6 +37,9 @@ def parser():
     ap.add_argument("--smooth", nargs="?", type=float, const=True, default=None, metavar="DEG",
                     help="smooth shading from interpolated vertex normals; DEG: the crease angle kept sharp "
                          "(default 40), even if the config entry has no \"smooth\" key")
+    ap.add_argument("--textures", action="store_true",
+                    help="the model's diffuse texture maps (OBJ vt, MTL map_Kd), even if the config entry has no "
+                         "\"textures\" key")
     return ap
 
 
@@ -96,7 +100,8 @@ def main(argv=None):
         return _main_dist(a)
     from .app import App
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
-              denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth)
+              denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth,
+              textures=True if a.textures else None)
     t0 = time.time()
     if a.frames:
         app.update(a.frames)
@@ -118,7 +123,7 @@ def _main_dist(a):
     from . import dist as D
     from . import render as R
     from . import scene as S
-    from .app import apply_environment, apply_smooth, config_scene
+    from .app import apply_environment, apply_smooth, apply_textures, config_scene
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # MCPT_DIST_SHARED_GPU=1 rehearses the N-rank job on a one-GPU box: every
     # rank on device 0, gloo for the one reduce (tests/test_gpu_dist.py)
@@ -143,6 +148,7 @@ def _main_dist(a):
     env = cli_environment(a, cfg)
     apply_environment(rnd, sc, cfg.ENVIRONMENT() if env is None else C.parse_environment(env), cfg, root)
     apply_smooth(rnd, sc, cli_smooth(a, cfg), cfg, root)  # and shades with its own copy of the vertex normals
+    textured = apply_textures(rnd, sc, a.textures or cfg.TEXTURES(), cfg, root)  # and of the textures
     w, h = cfg.WIDTH(), cfg.HEIGHT()
     frames = a.frames or cfg.MAXATTEPMT() + 1
     out = D.render_distributed(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, cfg.MAXDEPTH(), cfg.MAXATTEPMT(),
@@ -158,7 +164,8 @@ def _main_dist(a):
             st.hist.copy_(torch.from_numpy(out[0]).view(-1, 4))
             st.count.copy_(torch.from_numpy(out[1]))
             hits = rnd.first_hits(sc, S.parse_camera(cfg.GETCAMERA()), w, h)
-            den = rnd.denoise(sc, hits, st).cpu().numpy().reshape(h, w, 4)
+            albedo = rnd.first_hit_albedo(sc, hits) if textured else None
+            den = rnd.denoise(sc, hits, st, albedo=albedo).cpu().numpy().reshape(h, w, 4)
             S.write_hdr(App.denoised_path(path), den, flip=True)
             print("wrote", App.denoised_path(path))
     dist.destroy_process_group()

@@ -68,6 +68,17 @@ class DenoiseParams(ctypes.Structure):
                 ("sigma_plane", ctypes.c_float), ("sigma_color", ctypes.c_float)]
 
 
+class TextureImage(ctypes.Structure):
+    """mcpt_texture_image: rgb (host float32, width * height * 3), width, height."""
+    _fields_ = [("rgb", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class Textures(ctypes.Structure):
+    """mcpt_textures: uv (n_tris x 6 float32), tri_tex (n_tris int32), n_textures, images."""
+    _fields_ = [("uv", ctypes.c_void_p), ("tri_tex", ctypes.c_void_p), ("n_textures", ctypes.c_int32),
+                ("images", ctypes.c_void_p)]
+
+
 class Environment(ctypes.Structure):
     """mcpt_environment: scale[4], map_rgb (host float32 RGB rows, or NULL),
     width, height, rotate_deg."""
@@ -107,6 +118,12 @@ SIGNATURES = {
     "mcpt_obj_normals_from_text": (_I32, [_P, _I64, _P, _P, _P]),
     "mcpt_scene_set_vertex_normals": (_I32, [_P, _P, _P]),
     "mcpt_shading_normals": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P]),
+    "mcpt_load_obj_uvs": (_I32, [_S, _S, _P, _P, _P]),
+    "mcpt_obj_uvs_from_text": (_I32, [_P, _I64, _P, _P, _P]),
+    "mcpt_load_mtl_maps": (_I32, [_S, _S, _P, _P, _P]),
+    "mcpt_mtl_maps_from_text": (_I32, [_P, _I64, _P, _P, _P]),
+    "mcpt_scene_set_textures": (_I32, [_P, _P, _P]),
+    "mcpt_texture_eval": (_I32, [_P, _P, _P, _P, _I64, _P, _P]),
     "mcpt_ctx_create": (_I32, [_I32, _P]),
     "mcpt_ctx_destroy": (_I32, [_P]),
     "mcpt_device_count": (_I32, [_P]),

@@ -33,6 +33,12 @@ OBJ file's `vn` records where it has them, generated ones elsewhere; creases
 sharper than the angle, default 40 degrees, stay creases) instead of the
 triangle's face normal (Renderer.set_vertex_normals).  The denoise pass's
 guide follows: first_hits returns the shading normals.
+
+Extension: "textures": true (App(..., textures=True), --textures) multiplies
+the diffuse lobe's Kd by the model's map_Kd texture at each hit (OBJ `vt`
+coordinates, bilinear, repeating, no mip levels; Renderer.set_textures).  The
+denoise pass then filters the image divided by the first hits' texture factor
+and multiplies it back (Renderer.denoise's albedo), so the texture stays sharp.
 """
 import os
 
@@ -92,9 +98,27 @@ def apply_smooth(renderer, scene, crease, cfg, root):
     renderer.set_vertex_normals(scene, S.smooth_normals(scene.data.tris, crease, authored))
 
 
+def apply_textures(renderer, scene, on, cfg, root):
+    """Set a config entry's model textures (OBJ vt, MTL map_Kd) on an uploaded
+    scene when `on`; returns whether the scene is textured now.  App.init and
+    every rank of the multi-GPU CLI go through this."""
+    if not on:
+        return False
+    directory = os.path.join(root, cfg.GETDIRECTORY())
+    if not directory.endswith("/"):
+        directory += "/"
+    tris = scene.data.tris
+    mat_index = np.ascontiguousarray(tris["normal"][:, 3]).view(np.int32)  # pack_triangles put it there
+    uv, tri_tex, images = S.load_textures(directory, cfg.GETOBJNAME(), scene.data.mats, mat_index)
+    if not (tri_tex >= 0).any():
+        return False
+    renderer.set_textures(scene, uv, tri_tex, images)
+    return True
+
+
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
-                 material_override=None, jitter=None, denoise=None, environment=None, smooth=None):
+                 material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -113,6 +137,8 @@ class App:
         self.environment = self.cfg.ENVIRONMENT() if environment is None else C.parse_environment(environment)
         # None: the entry's "smooth" key; else that key's value (True / False / crease degrees)
         self.smooth = self.cfg.SMOOTH() if smooth is None else C.parse_smooth(smooth)
+        self.textures = self.cfg.TEXTURES() if textures is None else C.parse_textures(textures)  # None: the entry's key
+        self.textured = False
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -133,6 +159,7 @@ class App:
         self.scene = self.renderer.upload(self.data)
         apply_environment(self.renderer, self.scene, self.environment, self.cfg, self.root)
         apply_smooth(self.renderer, self.scene, self.smooth, self.cfg, self.root)
+        self.textured = apply_textures(self.renderer, self.scene, self.textures, self.cfg, self.root)
         self.state = self.renderer.new_state(self.w, self.h, self.seeds)
         self._init = True
 
@@ -182,9 +209,12 @@ class App:
         hits; the state is only read."""
         if not self._init:
             self.init()
+        return self._denoise().cpu().numpy().reshape(self.h, self.w, 4)
+
+    def _denoise(self):
         hits = self.renderer.first_hits(self.scene, self.camera, self.w, self.h)
-        out = self.renderer.denoise(self.scene, hits, self.state)
-        return out.cpu().numpy().reshape(self.h, self.w, 4)
+        albedo = self.renderer.first_hit_albedo(self.scene, hits) if self.textured else None
+        return self.renderer.denoise(self.scene, hits, self.state, albedo=albedo)
 
     def run(self):
         self.update(self.cfg.MAXATTEPMT() + 1)
@@ -202,7 +232,6 @@ class App:
             self.init()
         src = self.state.hist
         if self.denoise:
-            hits = self.renderer.first_hits(self.scene, self.camera, self.w, self.h)
-            src = self.renderer.denoise(self.scene, hits, self.state)
+            src = self._denoise()
         out = self.renderer.gamma_preview(src)
         return out.cpu().numpy().reshape(self.h, self.w, 4)

@@ -74,6 +74,13 @@ def parse_smooth(v):
     return float(v)
 
 
+def parse_textures(v):
+    """The "textures" extension key of a config entry -> bool."""
+    if not isinstance(v, bool):
+        raise ValueError('config "textures" must be true or false, got %r' % (v,))
+    return v
+
+
 def parse_environment(e):
     """The "environment" extension key of a config entry ->
     {"scale": (r, g, b), "map": path or None, "rotate": degrees}.
@@ -134,6 +141,9 @@ class Config:
         # "smooth": true | <crease degrees>: shade with interpolated vertex normals
         # (Renderer.set_vertex_normals); None: the reference's face normals
         self.smooth = parse_smooth(c["smooth"]) if "smooth" in c else None
+        # "textures": true: the model's diffuse texture maps (OBJ vt, MTL map_Kd;
+        # Renderer.set_textures); false: the materials' Kd alone, as the reference
+        self.textures = parse_textures(c["textures"]) if "textures" in c else False
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -178,3 +188,4 @@ class Config:
     def DENOISE(self): return self.denoise  # extension: the denoise post-pass
     def ENVIRONMENT(self): return self.environment  # extension: parse_environment's dict, or None
     def SMOOTH(self): return self.smooth  # extension: smooth shading's crease angle in degrees, or None
+    def TEXTURES(self): return self.textures  # extension: the model's map_Kd textures on the diffuse lobe

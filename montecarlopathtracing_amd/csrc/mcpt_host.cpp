@@ -1033,3 +1033,221 @@ extern "C" int mcpt_load_obj_normals(const char *directory, const char *objname,
   if (!read_file(dir + objname, &text)) return fail(MCPT_ERR_IO, "load_obj_normals: cannot read " + dir + objname);
   return mcpt_obj_normals_from_text(text.data(), (int64_t)text.size(), vn, has, n_tris);
 }
+
+// ------------------------------------------------- texture maps (opt-in)
+namespace {
+
+// Field k (0: v, 1: vt, 2: vn) of an OBJ face corner "v", "v/vt", "v//vn",
+// "v/vt/vn": 0 absent or empty, 1 a number in *out, -1 not a usable number
+int corner_field(const char *p, const char *e, int k, long *out) {
+  for (int f = 0; f < k; ++f) {
+    while (p < e && *p != '/') ++p;
+    if (p == e) return 0;
+    ++p;  // the slash
+  }
+  const char *s = p;
+  while (p < e && *p != '/') ++p;
+  if (p == s) return 0;
+  if (p - s >= 24) return -1;
+  const std::string t(s, p);
+  char *stop = nullptr;
+  *out = std::strtol(t.c_str(), &stop, 10);  // saturates: an overflowing index is out of range below
+  return stop == t.c_str() + t.size() ? 1 : -1;
+}
+
+bool whole_number(const char *p, const char *e) {
+  if (p == e || e - p >= 64) return false;
+  const std::string t(p, e);
+  char *stop = nullptr;
+  (void)std::strtod(t.c_str(), &stop);
+  return stop == t.c_str() + t.size();
+}
+
+// The file name of a map_Kd line's arguments [q, eol): options first (skipped,
+// not honoured), then the name, which may hold spaces; backslashes become slashes
+std::string map_name(const char *q, const char *eol) {
+  static const char *const one[] = {"-blendu", "-blendv", "-clamp", "-cc", "-imfchan", "-type", "-texres", "-boost", "-bm"};
+  for (;;) {
+    while (q < eol && (*q == ' ' || *q == '\t')) ++q;
+    const char *save = q;
+    Tok t = next_token(q, eol);
+    if (t.p == t.e) return std::string();
+    const std::string k(t.p, t.e);
+    int fixed = -1;
+    for (const char *o : one)
+      if (k == o) fixed = 1;
+    if (k == "-mm") fixed = 2;
+    if (fixed >= 0) {
+      for (int a = 0; a < fixed; ++a) (void)next_token(q, eol);
+      continue;
+    }
+    if (k == "-o" || k == "-s" || k == "-t") {  // one to three numbers
+      for (int a = 0; a < 3; ++a) {
+        const char *peek = q;
+        Tok n = next_token(peek, eol);
+        if (!whole_number(n.p, n.e)) break;
+        q = peek;
+      }
+      continue;
+    }
+    const char *ne = eol;
+    while (ne > save && (ne[-1] == '\r' || ne[-1] == ' ' || ne[-1] == '\t' || ne[-1] == '\n')) --ne;
+    std::string name(save, ne);
+    for (char &c : name)
+      if (c == '\\') c = '/';
+    return name;
+  }
+}
+
+// parse_mtl's records, their map_Kd names alone (the same order: one per newmtl)
+void parse_mtl_maps(const char *p, const char *end, std::vector<std::string> *maps) {
+  bool have = false;
+  while (p < end) {
+    const char *eol = (const char *)std::memchr(p, '\n', end - p);
+    if (!eol) eol = end;
+    const char *q = p;
+    Tok key = next_token(q, eol);
+    const std::string k(key.p, key.e);
+    if (k == "newmtl") {
+      maps->push_back(std::string());
+      have = true;
+    } else if (k == "map_Kd" && have) {
+      maps->back() = map_name(q, eol);
+    }
+    p = eol + 1;
+  }
+}
+
+int emit_maps(const std::vector<std::string> &maps, char *names, int64_t *n_bytes, int64_t *n_materials) {
+  int64_t need = 0;
+  for (const std::string &m : maps) need += (int64_t)m.size() + 1;
+  if (names) {
+    if (*n_bytes < need) return fail(MCPT_ERR_ARG, "mtl_maps: name buffer too small");
+    char *w = names;
+    for (const std::string &m : maps) {
+      // (a name never holds '\0': an embedded one ends it here)
+      const size_t l = std::strlen(m.c_str());
+      std::memcpy(w, m.c_str(), l);
+      w += l;
+      *w++ = '\0';
+    }
+    need = (int64_t)(w - names);
+  }
+  *n_bytes = need;
+  *n_materials = (int64_t)maps.size();
+  return MCPT_OK;
+}
+
+}  // namespace
+
+extern "C" int mcpt_obj_uvs_from_text(const char *text, int64_t len, float *uv, uint8_t *has, int64_t *n_tris) {
+  if (!n_tris || len < 0 || (len > 0 && !text)) return fail(MCPT_ERR_ARG, "obj_uvs: bad argument");
+  std::vector<double> coords;  // the vt records' (u, v), as parsed
+  struct FaceT {
+    long t[3];  // 0-based vt index per corner, -1: none
+  };
+  std::vector<FaceT> faces;
+  std::vector<long> poly;
+  const char *p = text, *end = text + len;
+  while (p < end) {
+    const char *eol = (const char *)std::memchr(p, '\n', end - p);
+    if (!eol) eol = end;
+    const char *q = p;
+    while (q < eol && (*q == ' ' || *q == '\t')) ++q;
+    if (q + 2 < eol && q[0] == 'v' && q[1] == 't' && (q[2] == ' ' || q[2] == '\t')) {
+      q += 3;
+      for (int k = 0; k < 2; ++k) {
+        Tok t = next_token(q, eol);
+        double v = 0.0;
+        if (!parse_number(t.p, t.e, &v)) v = k == 0 ? NAN : 0.0;  // "vt u" alone is (u, 0); no u: not usable
+        coords.push_back(v);
+      }
+    } else if (q + 1 < eol && q[0] == 'f' && (q[1] == ' ' || q[1] == '\t')) {
+      q += 2;
+      poly.clear();
+      const long nvt = (long)(coords.size() / 2);
+      for (;;) {
+        Tok t = next_token(q, eol);
+        if (t.p == t.e) break;
+        long v = 0, vt = 0;
+        if (corner_field(t.p, t.e, 0, &v) != 1 || v == 0) return fail(MCPT_ERR_PARSE, "obj_uvs: bad face index");  // as mcpt_load_obj
+        const int got = corner_field(t.p, t.e, 1, &vt);
+        if (got < 0 || (got == 1 && vt == 0)) return fail(MCPT_ERR_PARSE, "obj_uvs: bad vt index");
+        if (got == 1 && (vt > nvt || (vt < 0 && vt < -nvt))) return fail(MCPT_ERR_PARSE, "obj_uvs: vt index out of range");
+        poly.push_back(got == 0 ? -1 : (vt > 0 ? vt - 1 : nvt + vt));
+      }
+      if (poly.size() < 3) {
+        p = eol + 1;
+        continue;
+      }
+      for (size_t k = 1; k + 1 < poly.size(); ++k) faces.push_back(FaceT{{poly[0], poly[k], poly[k + 1]}});
+    }
+    p = eol + 1;
+  }
+  if (uv || has) {
+    if (!uv || !has) return fail(MCPT_ERR_ARG, "obj_uvs: uv and has come together");
+    if (*n_tris < (int64_t)faces.size()) return fail(MCPT_ERR_ARG, "obj_uvs: buffers too small");
+    for (size_t i = 0; i < faces.size(); ++i) {
+      bool ok = true;
+      float out[6] = {0, 0, 0, 0, 0, 0};
+      for (int k = 0; k < 3 && ok; ++k) {
+        if (faces[i].t[k] < 0) {
+          ok = false;
+          break;
+        }
+        const double *c = &coords[2 * (size_t)faces[i].t[k]];
+        out[2 * k] = (float)c[0], out[2 * k + 1] = (float)c[1];
+        ok = std::isfinite(out[2 * k]) && std::isfinite(out[2 * k + 1]);
+      }
+      if (!ok) std::memset(out, 0, sizeof out);
+      std::memcpy(uv + 6 * i, out, sizeof out);
+      has[i] = ok ? 1 : 0;
+    }
+  }
+  *n_tris = (int64_t)faces.size();
+  return MCPT_OK;
+}
+
+extern "C" int mcpt_load_obj_uvs(const char *directory, const char *objname, float *uv, uint8_t *has, int64_t *n_tris) {
+  if (!directory || !objname || !n_tris) return fail(MCPT_ERR_ARG, "load_obj_uvs: null argument");
+  std::string dir(directory), text;
+  if (!read_file(dir + objname, &text)) return fail(MCPT_ERR_IO, "load_obj_uvs: cannot read " + dir + objname);
+  return mcpt_obj_uvs_from_text(text.data(), (int64_t)text.size(), uv, has, n_tris);
+}
+
+extern "C" int mcpt_mtl_maps_from_text(const char *text, int64_t len, char *names, int64_t *n_bytes,
+                                       int64_t *n_materials) {
+  if (!n_bytes || !n_materials || len < 0 || (len > 0 && !text)) return fail(MCPT_ERR_ARG, "mtl_maps: bad argument");
+  std::vector<std::string> maps;
+  parse_mtl_maps(text, text + len, &maps);
+  return emit_maps(maps, names, n_bytes, n_materials);
+}
+
+extern "C" int mcpt_load_mtl_maps(const char *directory, const char *objname, char *names, int64_t *n_bytes,
+                                  int64_t *n_materials) {
+  if (!directory || !objname || !n_bytes || !n_materials) return fail(MCPT_ERR_ARG, "load_mtl_maps: null argument");
+  std::string dir(directory), text;
+  if (!read_file(dir + objname, &text)) return fail(MCPT_ERR_IO, "load_mtl_maps: cannot read " + dir + objname);
+  std::vector<std::string> maps;
+  const char *p = text.data(), *end = p + text.size();
+  while (p < end) {  // mcpt_load_obj's mtllib rule: of each line, the first library that loads
+    const char *eol = (const char *)std::memchr(p, '\n', end - p);
+    if (!eol) eol = end;
+    const char *q = p;
+    while (q < eol && (*q == ' ' || *q == '\t')) ++q;
+    if (eol - q >= 6 && std::strncmp(q, "mtllib", 6) == 0 && (q[6] == ' ' || q[6] == '\t')) {
+      q += 7;
+      for (;;) {
+        Tok t = next_token(q, eol);
+        if (t.p == t.e) break;
+        std::string mt;
+        if (read_file(dir + std::string(t.p, t.e), &mt)) {
+          parse_mtl_maps(mt.data(), mt.data() + mt.size(), &maps);
+          break;
+        }
+      }
+    }
+    p = eol + 1;
+  }
+  return emit_maps(maps, names, n_bytes, n_materials);
+}

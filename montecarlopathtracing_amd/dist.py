@@ -62,17 +62,21 @@ def reduce_image(hist, count, seeds, mask, group=None, dst=0):
 
 
 def render_distributed(renderer, scene, camera, width, height, max_depth, max_attempt, frames, seeds,
-                       stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None):
+                       stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None, textures=None):
     """Render the whole image across the process group; rank 0 gets the image.
     `jitter`: Renderer.render_frames' sub-pixel jitter (per-pixel draws, so
     still the single-GPU image for any GPU count).  `vertex_normals`: smooth
     shading's (n_tris, 3, 3) normals, set on this rank's scene before it
     renders (Renderer.set_vertex_normals; None: the scene as it is), so every
-    rank shades its stripes with the same ones.
+    rank shades its stripes with the same ones.  `textures`: a (uv, tri_tex,
+    images) triple (scene.load_textures'), set on this rank's scene likewise
+    (Renderer.set_textures).
     Returns (hist, count, seeds) as numpy on rank 0, None elsewhere."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if vertex_normals is not None:
         renderer.set_vertex_normals(scene, vertex_normals)
+    if textures is not None:
+        renderer.set_textures(scene, *textures)
     st = renderer.new_state(width, height, seeds)
     kw = dict(stripe_rows=stripe_rows, stripe_index=rank, stripe_count=world, mode=mode, jitter=jitter)
     if frames >= 4096:  # long runs: each rank times the leaf schedules and S/fetch thresholds on one-block

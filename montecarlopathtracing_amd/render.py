@@ -529,19 +529,95 @@ class Renderer:
         torch.cuda.current_stream().synchronize()  # (the inputs above are temporaries)
         return out
 
+    # ------------------------------------------------- texture maps (opt-in)
+    def set_textures(self, scene, uv, tri_tex, images):
+        """mcpt_scene_set_textures: the diffuse lobe's kd on `scene` is
+        multiplied by the bilinear, repeating lookup of each hit's texture.
+        uv: (n_tris, 3, 2) float32 in the upload's triangle order; tri_tex:
+        n_tris int32 indices into `images`, -1: no texture; images: (h, w, 3)
+        linear float32 arrays, row 0 the top (scene.load_textures returns the
+        three).  Replaces previous ones and drops the primary-hit cache."""
+        u = np.ascontiguousarray(uv, np.float32)
+        t = np.ascontiguousarray(tri_tex, np.int32)
+        n = len(scene.data.tris) if hasattr(scene.data, "tris") else scene.data[0].numel() // L.TRIANGLE.itemsize
+        if u.size != n * 6 or t.size != n:
+            raise ValueError("set_textures: %d triangles need (n, 3, 2) uvs and n indices, got %r and %r" %
+                             (n, u.shape, t.shape))
+        imgs = [np.ascontiguousarray(im, np.float32) for im in images]
+        for k, im in enumerate(imgs):
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("set_textures: image %d must be (height, width, 3), got %r" % (k, im.shape))
+        recs = (L.TextureImage * max(len(imgs), 1))()
+        for k, im in enumerate(imgs):
+            recs[k].rgb, recs[k].width, recs[k].height = L.ptr(im), im.shape[1], im.shape[0]
+        tx = L.Textures(L.ptr(u), L.ptr(t), len(imgs), ctypes.cast(recs, ctypes.c_void_p))
+        L.check(L.lib().mcpt_scene_set_textures(self.ctx, scene.handle, ctypes.byref(tx)))
+
+    def clear_textures(self, scene):
+        """Back to the materials' kd (the bits of a scene that never had textures)."""
+        L.check(L.lib().mcpt_scene_set_textures(self.ctx, scene.handle, None))
+
+    def texture_eval(self, scene, tri_ids, points):
+        """mcpt_texture_eval: kd's factor at (triangle, hit point) queries on a
+        textured scene: a float32 (n, 4) device tensor (w = 1; zeros for an
+        index outside the scene).  tri_ids: n int32, host or device; points:
+        (n, 3) or (n, 4), host or a device (n, 4) float32 tensor."""
+        if torch.is_tensor(tri_ids):
+            ids = tri_ids.to(self.device, torch.int32).contiguous()
+        else:
+            ids = torch.as_tensor(np.ascontiguousarray(tri_ids, np.int32)).to(self.device)
+        n = ids.numel()
+        if torch.is_tensor(points):
+            p = points.to(self.device, torch.float32).reshape(n, 4).contiguous()
+        else:
+            a = np.asarray(points, np.float32).reshape(n, -1)
+            q = np.zeros((n, 4), np.float32)
+            q[:, :a.shape[1]] = a
+            p = torch.from_numpy(q).to(self.device)
+        out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        L.check(L.lib().mcpt_texture_eval(self.ctx, scene.handle, L.ptr(ids), L.ptr(p), n, L.ptr(out), _stream()))
+        torch.cuda.current_stream().synchronize()  # (the inputs above are temporaries)
+        return out
+
+    def first_hit_albedo(self, scene, hits):
+        """Renderer.denoise's `albedo` for a textured scene: texture_eval at
+        the first hits (first_hits' records), forced to 1 where the first hit
+        is a miss or not MCPT_DIFFUSE / MCPT_GLOSSY, so that those pixels keep
+        their bits.  A float32 (n, 4) device tensor."""
+        h = records(hits, L.HIT)
+        mats = scene.data.mats if hasattr(scene.data, "mats") else None
+        hit = h["t"] < np.float32(3.0e38)
+        ids = np.where(hit, h["triangle_id"].astype(np.int64), 0).astype(np.int32)
+        a = self.texture_eval(scene, ids, h["point"]).cpu().numpy()
+        keep = hit.copy()
+        if mats is not None and len(mats):
+            ty = np.asarray(mats["type"])[np.clip(h["material_id"].astype(np.int64), 0, len(mats) - 1)]
+            keep &= (ty == L.MCPT_DIFFUSE) | (ty == L.MCPT_GLOSSY)
+        a[~keep] = 1.0
+        a[:, 3] = 1.0
+        return torch.from_numpy(a).to(self.device)
+
     # ------------------------------------------------------ denoise (opt-in)
     def first_hits(self, scene, camera, width, height, mode=L.MODE_EXACT):
         """Every pixel's first hit (W*H Hit records, device bytes): generate_rays
         then intersect, the corner ray's also when the render is jittered."""
         return self.intersect(scene, self.generate_rays(camera, width, height), mode=mode)
 
-    def denoise(self, scene, hits, state, iterations=None, sigma_normal=None, sigma_plane=None, sigma_color=None):
+    def denoise(self, scene, hits, state, iterations=None, sigma_normal=None, sigma_plane=None, sigma_color=None,
+                albedo=None):
         """mcpt_denoise: the count-aware, geometry-guided a-trous filter of
         state.hist, guided by `hits` (first_hits of the same view), into a new
         float32 (n, 4) device tensor.  Reads the state, writes none of it.
         None takes the default of DENOISE_DEFAULTS (iterations 0..8, 0 copies
         hist; sigma_plane a fraction of the scene diagonal; sigma_color 0
-        switches the colour term off)."""
+        switches the colour term off).
+        `albedo`: a float32 (n, 3) or (n, 4) array or device tensor, the
+        texture factor at each pixel's first hit (first_hit_albedo): the filter
+        then runs on hist / a' and a' is multiplied back, a' = max(a, 2^-8)
+        per channel, so that a texture is not smeared across the pixels of one
+        material and plane.  Exact for the diffuse lobe, approximate for glossy
+        (whose specular lobe carries no texture).  mcpt_denoise itself is the
+        same either way; a pixel whose a is 1 keeps the bits it has without."""
         n = state.width * state.height
         if not hits.is_cuda or hits.numel() * hits.element_size() != n * L.HIT.itemsize:
             raise L.MCPTError("denoise: hits must be the state's width*height Hit records on the GPU")
@@ -551,8 +627,19 @@ class Renderer:
         p = L.DenoiseParams(int(v["iterations"]), float(v["sigma_normal"]), float(v["sigma_plane"]),
                             float(v["sigma_color"]))
         out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
-        L.check(L.lib().mcpt_denoise(self.ctx, scene.handle, L.ptr(hits), L.ptr(state.hist), L.ptr(state.count),
+        hist, a = state.hist, None
+        if albedo is not None:
+            a = torch.as_tensor(albedo, dtype=torch.float32).to(self.device).reshape(n, -1)
+            if a.shape[1] not in (3, 4):
+                raise ValueError("denoise: albedo must be (n, 3) or (n, 4)")
+            a4 = torch.ones((n, 4), dtype=torch.float32, device=self.device)
+            a4[:, :3] = torch.clamp(a[:, :3], min=2.0 ** -8)
+            a = a4
+            hist = (state.hist.reshape(n, 4) / a).contiguous()
+        L.check(L.lib().mcpt_denoise(self.ctx, scene.handle, L.ptr(hits), L.ptr(hist), L.ptr(state.count),
                                      state.width, state.height, ctypes.byref(p), L.ptr(out), _stream()))
+        if a is not None:
+            out = out * a
         return out
 
 

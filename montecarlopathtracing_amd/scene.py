@@ -180,6 +180,232 @@ def write_png(path, preview, flip=True):
     return path
 
 
+# ------------------------------------------------------ texture maps (opt-in)
+def _srgb_table():
+    """8-bit sRGB -> linear float32: c <= 0.04045 ? c / 12.92 : ((c + 0.055) /
+    1.055)^2.4 with c = i / 255, computed in float64 and rounded once."""
+    c = np.arange(256, dtype=np.float64) / 255.0
+    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4).astype(np.float32)
+
+
+SRGB_TO_LINEAR = _srgb_table()
+
+
+def decode_png(data):
+    """PNG bytes -> (height, width, 3) uint8, row 0 the top.  8-bit,
+    non-interlaced images of colour types 0 (grey), 2 (RGB), 3 (palette), 4
+    (grey + alpha) and 6 (RGBA), all five row filters; alpha is dropped.
+    Anything else raises ValueError.  Needs zlib only."""
+    import struct
+    import zlib
+    data = bytes(data)
+    if data[:8] != b"\x89PNG\r\n\x1a\n":
+        raise ValueError("not a PNG file")
+    pos, ihdr, plte, idat, ended = 8, None, None, [], False
+    while pos + 8 <= len(data) and not ended:
+        n, tag = struct.unpack(">I4s", data[pos:pos + 8])
+        body = data[pos + 8:pos + 8 + n]
+        if len(body) != n or pos + 12 + n > len(data):
+            raise ValueError("PNG: truncated %s chunk" % tag.decode("latin-1"))
+        if struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])[0] != (zlib.crc32(tag + body) & 0xFFFFFFFF):
+            raise ValueError("PNG: bad checksum in %s chunk" % tag.decode("latin-1"))
+        if tag == b"IHDR":
+            ihdr = body
+        elif tag == b"PLTE":
+            plte = body
+        elif tag == b"IDAT":
+            idat.append(body)
+        elif tag == b"IEND":
+            ended = True
+        pos += 12 + n
+    if ihdr is None or len(ihdr) != 13 or not idat or not ended:
+        raise ValueError("PNG: missing IHDR, IDAT or IEND")
+    w, h, depth, ctype, comp, filt, lace = struct.unpack(">IIBBBBB", ihdr)
+    if depth != 8 or ctype not in (0, 2, 3, 4, 6) or comp != 0 or filt != 0 or lace != 0:
+        raise ValueError("PNG: only 8-bit, non-interlaced images of colour type 0, 2, 3, 4 or 6 are read "
+                         "(depth %d, colour type %d, interlace %d)" % (depth, ctype, lace))
+    if not (1 <= w <= 16384 and 1 <= h <= 16384):
+        raise ValueError("PNG: %d x %d is outside 1..16384" % (w, h))
+    bpp = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}[ctype]
+    stride = w * bpp
+    try:
+        raw = zlib.decompress(b"".join(idat))
+    except zlib.error as e:
+        raise ValueError("PNG: %s" % e)
+    if len(raw) != h * (stride + 1):
+        raise ValueError("PNG: %d bytes of image data, expected %d" % (len(raw), h * (stride + 1)))
+    rows = np.frombuffer(raw, np.uint8).reshape(h, stride + 1)
+    out = np.zeros((h, stride), np.uint8)
+    prev = np.zeros(stride, np.int32)
+    for y in range(h):
+        f, line = int(rows[y, 0]), rows[y, 1:].astype(np.int32)
+        if f == 0:
+            cur = line
+        elif f == 2:
+            cur = (line + prev) & 255
+        elif f == 1:  # Sub: a running sum per byte lane of a pixel
+            cur = np.cumsum(line.reshape(w, bpp), axis=0).reshape(-1) & 255
+        elif f in (3, 4):  # Average, Paeth: each byte needs the finished one to its left
+            cur = np.zeros(stride, np.int32)
+            up = prev.tolist()
+            ln = line.tolist()
+            c = [0] * stride
+            for i in range(stride):
+                a = c[i - bpp] if i >= bpp else 0
+                b = up[i]
+                if f == 3:
+                    pred = (a + b) >> 1
+                else:
+                    cc = up[i - bpp] if i >= bpp else 0
+                    pp = a + b - cc
+                    pa, pb, pc = abs(pp - a), abs(pp - b), abs(pp - cc)
+                    pred = a if (pa <= pb and pa <= pc) else (b if pb <= pc else cc)
+                c[i] = (ln[i] + pred) & 255
+            cur = np.asarray(c, np.int32)
+        else:
+            raise ValueError("PNG: row filter %d" % f)
+        out[y] = cur
+        prev = cur
+    px = out.reshape(h, w, bpp)
+    if ctype == 3:
+        if plte is None or len(plte) % 3 or not plte:
+            raise ValueError("PNG: palette image without a palette")
+        pal = np.frombuffer(plte, np.uint8).reshape(-1, 3)
+        if int(px.max()) >= len(pal):
+            raise ValueError("PNG: palette index out of range")
+        return np.ascontiguousarray(pal[px[..., 0]])
+    if ctype in (0, 4):
+        return np.ascontiguousarray(np.repeat(px[..., :1], 3, axis=2))
+    return np.ascontiguousarray(px[..., :3])
+
+
+def read_png(path):
+    """A PNG file as (height, width, 3) uint8, row 0 the top (decode_png)."""
+    with open(path, "rb") as fh:
+        try:
+            return decode_png(fh.read())
+        except ValueError as e:
+            raise ValueError("%s: %s" % (path, e))
+
+
+def read_texture(path):
+    """A texture image as (height, width, 3) linear float32, row 0 the top:
+    .png through read_png and .hdr through read_hdr (taken as linear); other
+    formats through Pillow if it is importable.  8-bit data is decoded from
+    sRGB with SRGB_TO_LINEAR.  A missing or unreadable file raises ValueError
+    naming it."""
+    import os
+    if not os.path.isfile(path):
+        raise ValueError("texture file %s does not exist" % path)
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".png":
+        return SRGB_TO_LINEAR[read_png(path)]
+    if ext == ".hdr":
+        try:
+            a = read_hdr(path)
+        except L.MCPTError as e:
+            raise ValueError("%s: %s" % (path, e))
+        return np.ascontiguousarray(np.maximum(np.nan_to_num(a, nan=0.0, posinf=3.0e38), 0.0), np.float32)
+    try:
+        from PIL import Image
+    except ImportError:
+        raise ValueError("%s: only .png (8-bit, non-interlaced) and .hdr textures are read without Pillow" % path)
+    try:
+        with Image.open(path) as im:
+            q = np.asarray(im.convert("RGB"), np.uint8)
+    except Exception as e:  # Pillow raises its own types for unknown or damaged files
+        raise ValueError("%s: %s" % (path, e))
+    return SRGB_TO_LINEAR[q]
+
+
+def load_obj_uvs(directory, objname):
+    """Texture coordinates of an OBJ file (its `vt` records): (uv[n, 3, 2]
+    float32, has[n] bool) in load_object's triangle order; has[i] is False
+    where a corner of triangle i names no finite vt (uv[i] is zero there)."""
+    lib = L.lib()
+    nt = ctypes.c_int64(0)
+    d, o = directory.encode(), objname.encode()
+    L.check(lib.mcpt_load_obj_uvs(d, o, None, None, ctypes.byref(nt)))
+    uv = np.zeros((nt.value, 3, 2), np.float32)
+    has = np.zeros(nt.value, np.uint8)
+    L.check(lib.mcpt_load_obj_uvs(d, o, L.ptr(uv), L.ptr(has), ctypes.byref(nt)))
+    return uv, has.astype(bool)
+
+
+def _names(buf, n):
+    parts = bytes(buf).split(b"\0")
+    return [x.decode("utf-8", "replace") for x in parts[:n]]
+
+
+def load_mtl_maps(directory, objname):
+    """Each material's map_Kd file name ("" without one), in load_object's
+    material order (mcpt_load_mtl_maps)."""
+    lib = L.lib()
+    nb, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+    d, o = directory.encode(), objname.encode()
+    L.check(lib.mcpt_load_mtl_maps(d, o, None, ctypes.byref(nb), ctypes.byref(nm)))
+    buf = np.zeros(max(nb.value, 1), np.uint8)
+    L.check(lib.mcpt_load_mtl_maps(d, o, L.ptr(buf), ctypes.byref(nb), ctypes.byref(nm)))
+    return _names(buf[:nb.value], nm.value)
+
+
+def mtl_maps_from_text(text):
+    """load_mtl_maps on MTL text (bytes or str) in memory."""
+    lib = L.lib()
+    t = text.encode() if isinstance(text, str) else bytes(text)
+    src = np.frombuffer(t, np.uint8) if t else np.zeros(0, np.uint8)
+    nb, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(lib.mcpt_mtl_maps_from_text(L.ptr(src) if len(src) else None, len(src), None, ctypes.byref(nb), ctypes.byref(nm)))
+    buf = np.zeros(max(nb.value, 1), np.uint8)
+    L.check(lib.mcpt_mtl_maps_from_text(L.ptr(src) if len(src) else None, len(src), L.ptr(buf), ctypes.byref(nb), ctypes.byref(nm)))
+    return _names(buf[:nb.value], nm.value)
+
+
+def obj_uvs_from_text(text):
+    """load_obj_uvs on OBJ text (bytes or str) in memory."""
+    lib = L.lib()
+    t = text.encode() if isinstance(text, str) else bytes(text)
+    src = np.frombuffer(t, np.uint8) if t else np.zeros(0, np.uint8)
+    sp = L.ptr(src) if len(src) else None
+    nt = ctypes.c_int64(0)
+    L.check(lib.mcpt_obj_uvs_from_text(sp, len(src), None, None, ctypes.byref(nt)))
+    uv = np.zeros((nt.value, 3, 2), np.float32)
+    has = np.zeros(nt.value, np.uint8)
+    L.check(lib.mcpt_obj_uvs_from_text(sp, len(src), L.ptr(uv), L.ptr(has), ctypes.byref(nt)))
+    return uv, has.astype(bool)
+
+
+def load_textures(directory, objname, mats, mat_index):
+    """What Renderer.set_textures takes for an OBJ model: (uv[n, 3, 2]
+    float32, tri_tex[n] int32, images: list of (h, w, 3) linear float32).
+    tri_tex[i] = -1 where triangle i has no `vt` or its material no map_Kd.
+    `mats` (load_object's, for their count) and `mat_index` (one per
+    triangle).  A named texture file that is missing raises ValueError naming
+    it; a model with maps but no `vt` at all comes back untextured after one
+    warning line."""
+    import os
+    import sys
+    uv, has = load_obj_uvs(directory, objname)
+    idx = np.asarray(mat_index, np.int32)
+    if len(idx) != len(uv):
+        raise ValueError("load_textures: %d material indices for %d triangles" % (len(idx), len(uv)))
+    names = load_mtl_maps(directory, objname)
+    names = (names + [""] * len(mats))[:max(len(mats), len(names))]
+    tri_tex = np.full(len(uv), -1, np.int32)
+    images, slot = [], {}
+    used = sorted(set(int(m) for m in idx[has] if 0 <= m < len(names) and names[m]))
+    for m in used:
+        path = os.path.join(directory, names[m])
+        if path not in slot:
+            slot[path] = len(images)
+            images.append(read_texture(path))
+        tri_tex[has & (idx == m)] = slot[path]
+    if any(names) and not has.any():
+        print("warning: %s names texture maps but has no texture coordinates (vt): rendering untextured" % objname,
+              file=sys.stderr)
+    return uv, tri_tex, images
+
+
 class SceneData:
     """Host-side scene: packed triangles, HLBVH nodes, materials."""
 

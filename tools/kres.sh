@@ -2,9 +2,10 @@
 # Register / scratch / occupancy of every k_render instantiation (compile-time, no GPU):
 #   bash tools/kres.sh [extra hipcc flags]
 #   bash tools/kres.sh -DMCPT_SMOOTH_TU     the smooth-shading (N) forms' translation unit instead
+#   bash tools/kres.sh -DMCPT_TEXTURE_TU    the textured forms' translation unit instead
 cd "$(dirname "$0")/../montecarlopathtracing_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on \
-  -fno-hip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function "$@" -c mcpt_device.hip -o /tmp/kres.o \
+  -fno-hip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function "$@" -c mcpt_device.hip -o /tmp/kres.$$.o \
   -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '
 import re, sys
 cur, res = None, {}
@@ -19,3 +20,4 @@ for k, v in res.items():
     if "k_render" in k:
         print(k, v)
 '
+rm -f /tmp/kres.$$.o
