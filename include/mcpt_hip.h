@@ -271,7 +271,9 @@ typedef struct mcpt_tuning {
  * mcpt_scene_set_vertex_normals, mcpt_shading_normals): functions only.
  * The texture entry points (mcpt_load_obj_uvs, mcpt_obj_uvs_from_text,
  * mcpt_load_mtl_maps, mcpt_mtl_maps_from_text, mcpt_scene_set_textures with
- * its own mcpt_textures, mcpt_texture_eval) came in at 5 likewise.
+ * its own mcpt_textures, mcpt_texture_eval) came in at 5 likewise, and so
+ * did the thin lens (mcpt_render_frames_lens and mcpt_generate_rays_lens with
+ * their own mcpt_lens).
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
 #define MCPT_ABI_VERSION 5
@@ -406,6 +408,51 @@ int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera
                        const mcpt_render_params *params, uint32_t *seeds_dev,
                        float *hist_dev, int32_t *count_dev, void *stream);
 
+/* Thin-lens camera (opt-in depth of field, no reference counterpart; ABI 5: a
+ * new struct with new entry points).  radius R >= 0 and focus_distance F > 0
+ * in scene units, both finite; F is measured along the view axis.
+ *
+ * mcpt_render_frames_lens is mcpt_render_frames with a lens.  A null lens or
+ * R == 0 means no lens: no draw is taken and the call is mcpt_render_frames'
+ * bit for bit, jittered or not.  R > 0 needs params->jitter == 1 (a lens needs
+ * a fresh primary ray per frame), else MCPT_ERR_ARG.  R < 0, F <= 0, or either
+ * not finite: MCPT_ERR_ARG, and nothing is touched.
+ *
+ * Draws, per pixel and frame, from the pixel's own seed chain: jx, jy as a
+ * jittered frame takes them, then r1 = lcg15(seed), r2 = lcg15(seed), then the
+ * frame's shading draws as before.
+ * Lens sample (the helpers of randomDirection): rho = sqrt(r1 * 2^-15) with
+ * the hardware square root, phi = 2 * pi * r2 / 32768 formed in double and
+ * rounded to float, (s, c) = sin, cos of phi, (a, b) = (rho * c, rho * s):
+ * uniform over the unit disk.
+ * Ray.  (o, d): the jittered generateRay's ray for (idx + jx, idy + jy), of
+ * either camera_type (the orthographic camera's o is its image-plane point, d
+ * the view direction).  c^, h^, u^: normalize() of the xyz of camera.direction,
+ * .horizontal and .up (horizontal and up are not unit vectors in general),
+ * computed once per launch.  Then
+ *     k  = F / dot(d, c^)
+ *     P  = o + k * d                   the sample's point on the focus plane
+ *     o' = o + R * (a * h^ + b * u^)   the point on the lens
+ *     d' = normalize(P - o')
+ * and o'.w, d'.w carry the bits they carried: depth 0 and the pixel id.
+ * Operation order (one device function, lens_ray of mcpt_lens.h, runs in both
+ * the fused kernel and mcpt_generate_rays_lens): A = R * (rho * c),
+ * B = R * (rho * s), off = fma(A, h^, B * u^) per component, k by the 2.5-ulp
+ * division, o' = o + off, d' = normalize(fma(k, d, -off)) (P - o' without the
+ * cancelling o).
+ * All lens rays of one sample meet at P, so geometry on the plane
+ * dot(x - o, c^) = F images as the jitter-only render does and everything
+ * else is blurred over a disk that grows linearly with its distance from that
+ * plane.  Such a call is a jittered call: it neither reads nor builds the
+ * primary-hit cache and leaves a held one valid.                            */
+typedef struct mcpt_lens {
+  float radius, focus_distance;
+  float pad[2];
+} mcpt_lens;
+int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_lens *lens,
+                            const mcpt_render_params *params, uint32_t *seeds_dev, float *hist_dev,
+                            int32_t *count_dev, void *stream);
+
 /* Launch-plan knobs (speed only), kept in the context; NULL resets them.  */
 int mcpt_set_tuning(mcpt_ctx *ctx, const mcpt_tuning *tuning);
 int mcpt_get_tuning(mcpt_ctx *ctx, mcpt_tuning *out);
@@ -447,6 +494,11 @@ int mcpt_generate_rays(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t width, int
  * advanced seed back to, seeds_dev[idy * width + idx].                     */
 int mcpt_generate_rays_jittered(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t width, int32_t height,
                                 uint32_t *seeds_dev, mcpt_ray *rays_dev, void *stream);
+/* mcpt_generate_rays_jittered plus the lens of mcpt_render_frames_lens: four
+ * draws a pixel (jx, jy, r1, r2).  A null lens or radius 0: the jittered
+ * call's bits, two draws.  A bad lens: MCPT_ERR_ARG.                        */
+int mcpt_generate_rays_lens(mcpt_ctx *ctx, const mcpt_camera *cam, const mcpt_lens *lens, int32_t width,
+                            int32_t height, uint32_t *seeds_dev, mcpt_ray *rays_dev, void *stream);
 /* intersect.cl intersectRays (tmin = EPSILON 1e-3, oclbasic.h:193)
  * Arbitrary rays (a unit direction is the callers' convention, not a
  * requirement).  MCPT_MODE_EXACT gives the reference kernel's t, normal,

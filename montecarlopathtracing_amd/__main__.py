@@ -3,7 +3,7 @@ or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
         [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]] [--smooth [DEG]]
-        [--textures]
+        [--textures] [--aperture R (--focus F | --focus-at X,Y)]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -40,7 +40,38 @@ def parser():
     ap.add_argument("--textures", action="store_true",
                     help="the model's diffuse texture maps (OBJ vt, MTL map_Kd), even if the config entry has no "
                          "\"textures\" key")
+    ap.add_argument("--aperture", type=float, default=None, metavar="R",
+                    help="thin-lens camera (depth of field): the lens radius in scene units; needs --focus or "
+                         "--focus-at, switches --jitter on, overrides the config entry's \"lens\"")
+    ap.add_argument("--focus", type=float, default=None, metavar="F",
+                    help="the distance along the view axis that is in focus, in scene units (with --aperture)")
+    ap.add_argument("--focus-at", default=None, metavar="X,Y",
+                    help="autofocus: focus on what pixel X,Y sees (with --aperture)")
     return ap
+
+
+def cli_lens(a):
+    """The command line's lens in the config key's form, or None: the entry's
+    own.  --aperture needs exactly one of --focus and --focus-at, and either
+    needs --aperture."""
+    focus = a.focus is not None or a.focus_at is not None
+    if a.aperture is None:
+        if focus:
+            raise ValueError("--focus and --focus-at need --aperture")
+        return None
+    if not focus:
+        raise ValueError("--aperture needs --focus or --focus-at")
+    if a.focus is not None and a.focus_at is not None:
+        raise ValueError("--focus and --focus-at exclude each other")
+    if a.focus is not None:
+        return {"aperture": a.aperture, "focus": a.focus}
+    try:
+        at = [int(x) for x in a.focus_at.split(",")]
+    except ValueError:
+        at = []
+    if len(at) != 2:
+        raise ValueError("--focus-at: expected a pixel X,Y, got %r" % (a.focus_at,))
+    return {"aperture": a.aperture, "focus_at": at}
 
 
 def cli_smooth(a, cfg):
@@ -101,7 +132,9 @@ def main(argv=None):
     from .app import App
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
               denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth,
-              textures=True if a.textures else None)
+              textures=True if a.textures else None, lens=cli_lens(a))
+    if app.lens_spec is not None:
+        print("lens: jitter switched on (a lens needs a fresh primary ray every frame)")
     t0 = time.time()
     if a.frames:
         app.update(a.frames)
@@ -123,7 +156,7 @@ def _main_dist(a):
     from . import dist as D
     from . import render as R
     from . import scene as S
-    from .app import apply_environment, apply_smooth, apply_textures, config_scene
+    from .app import apply_environment, apply_smooth, apply_textures, config_scene, resolve_lens
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # MCPT_DIST_SHARED_GPU=1 rehearses the N-rank job on a one-GPU box: every
     # rank on device 0, gloo for the one reduce (tests/test_gpu_dist.py)
@@ -151,8 +184,11 @@ def _main_dist(a):
     textured = apply_textures(rnd, sc, a.textures or cfg.TEXTURES(), cfg, root)  # and of the textures
     w, h = cfg.WIDTH(), cfg.HEIGHT()
     frames = a.frames or cfg.MAXATTEPMT() + 1
+    spec = cli_lens(a)
+    spec = cfg.LENS() if spec is None else C.parse_lens(spec)
+    lens = resolve_lens(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, spec)  # every rank: the same lens
     out = D.render_distributed(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, cfg.MAXDEPTH(), cfg.MAXATTEPMT(),
-                               frames, R.default_seeds(w * h), jitter=a.jitter or cfg.JITTER())
+                               frames, R.default_seeds(w * h), jitter=a.jitter or cfg.JITTER(), lens=lens)
     if dist.get_rank() == 0:
         path = os.path.join(a.out, cfg.GETOBJNAME() + ".hdr")
         S.write_hdr(path, out[0].reshape(h, w, 4), flip=True)

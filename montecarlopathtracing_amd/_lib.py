@@ -86,6 +86,11 @@ class Environment(ctypes.Structure):
                 ("width", ctypes.c_int32), ("height", ctypes.c_int32), ("rotate_deg", ctypes.c_float)]
 
 
+class Lens(ctypes.Structure):
+    """mcpt_lens (16 B): radius, focus_distance, pad[2]."""
+    _fields_ = [("radius", ctypes.c_float), ("focus_distance", ctypes.c_float), ("pad", ctypes.c_float * 2)]
+
+
 class MCPTError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -132,6 +137,8 @@ SIGNATURES = {
     "mcpt_scene_upload_device": (_I32, [_P, _P, _I64, _P, _I64, _P, _I32, _P, _P]),
     "mcpt_scene_read": (_I32, [_P, _I32, _P, _I64, _P]),
     "mcpt_render_frames": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcpt_render_frames_lens": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcpt_generate_rays_lens": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     "mcpt_generate_rays": (_I32, [_P, _P, _I32, _I32, _P, _P]),
     "mcpt_generate_rays_jittered": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
     "mcpt_intersect": (_I32, [_P, _P, _P, _I64, _P, _F32, _I32, _P]),

@@ -39,6 +39,15 @@ the diffuse lobe's Kd by the model's map_Kd texture at each hit (OBJ `vt`
 coordinates, bilinear, repeating, no mip levels; Renderer.set_textures).  The
 denoise pass then filters the image divided by the first hits' texture factor
 and multiplies it back (Renderer.denoise's albedo), so the texture stays sharp.
+
+Extension: "lens": {"aperture": R, "focus": F} or {"aperture": R, "focus_at":
+[px, py]} (App(..., lens={...} or (R, F)), --aperture with --focus or
+--focus-at) renders through a thin lens of radius R focused at distance F
+along the view axis, or on what pixel (px, py) sees (autofocus): depth of field
+instead of the reference's pinhole (Renderer.render_frames' lens).  A lens
+needs a fresh primary ray every frame, so it switches jitter on (App.jitter
+then reads True).  The denoise pass's guide stays the pinhole corner ray's
+first hit, as with jitter.
 """
 import os
 
@@ -116,9 +125,22 @@ def apply_textures(renderer, scene, on, cfg, root):
     return True
 
 
+def resolve_lens(renderer, scene, camera, width, height, spec):
+    """A lens spec (config.parse_lens' dict, or None) -> (R, F) or None; a
+    "focus_at" pixel is focused on through Renderer.autofocus.  App.init and
+    every rank of the multi-GPU CLI go through this."""
+    if spec is None:
+        return None
+    if spec["focus"] is not None:
+        return (spec["aperture"], spec["focus"])
+    px, py = spec["focus_at"]
+    return (spec["aperture"], renderer.autofocus(scene, camera, width, height, px, py))
+
+
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
-                 material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None):
+                 material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None,
+                 lens=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -138,6 +160,18 @@ class App:
         # None: the entry's "smooth" key; else that key's value (True / False / crease degrees)
         self.smooth = self.cfg.SMOOTH() if smooth is None else C.parse_smooth(smooth)
         self.textures = self.cfg.TEXTURES() if textures is None else C.parse_textures(textures)  # None: the entry's key
+        # None: the entry's "lens" key; else that key's value, or (R, F).  A lens switches jitter on.
+        if lens is None:
+            self.lens_spec = self.cfg.LENS()
+        elif isinstance(lens, dict):
+            self.lens_spec = C.parse_lens(lens)
+        else:
+            self.lens_spec = C.parse_lens({"aperture": lens[0], "focus": lens[1]})
+        if self.lens_spec is not None:
+            if jitter is not None and not jitter:
+                raise ValueError("a lens needs jitter: jitter=False cannot go with a lens")
+            self.jitter = True
+        self.lens = None  # (R, F) once init() has resolved the focus
         self.textured = False
         self.attempt_count = 0
         self.dumped = None
@@ -161,6 +195,7 @@ class App:
         apply_smooth(self.renderer, self.scene, self.smooth, self.cfg, self.root)
         self.textured = apply_textures(self.renderer, self.scene, self.textures, self.cfg, self.root)
         self.state = self.renderer.new_state(self.w, self.h, self.seeds)
+        self.lens = resolve_lens(self.renderer, self.scene, self.camera, self.w, self.h, self.lens_spec)
         self._init = True
 
     def update(self, frames=1):
@@ -177,12 +212,12 @@ class App:
             # one-block trials of either would tune a regime the run never enters.
             self.renderer.tune(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, frames=16,
                                block_entries=None, last_block=False, tile_orders=None, frames_per_launch=16,
-                               jitter=self.jitter)
+                               jitter=self.jitter, lens=self.lens)
             self._tuned = True
         while todo > 0:
             n = todo if self.attempt_count > att else min(todo, att + 1 - self.attempt_count)
             self.renderer.render_frames(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, n,
-                                        jitter=self.jitter)
+                                        jitter=self.jitter, lens=self.lens)
             self.attempt_count += n
             todo -= n
             if self.attempt_count > att and self.dumped is None:

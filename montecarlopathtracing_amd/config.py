@@ -81,6 +81,41 @@ def parse_textures(v):
     return v
 
 
+def parse_lens(v):
+    """The "lens" extension key of a config entry ->
+    {"aperture": R, "focus": F or None, "focus_at": (px, py) or None}.
+    {"aperture": R, "focus": F}: a thin lens of radius R focused at distance F
+    along the view axis, both > 0 in scene units.  {"aperture": R, "focus_at":
+    [px, py]}: focused on what that pixel sees (autofocus, Renderer.autofocus).
+    ValueError on wrong types, unknown keys, both or neither of "focus" and
+    "focus_at", and non-positive or non-finite values."""
+    if not isinstance(v, dict):
+        raise ValueError('config "lens" must be an object, got %r' % (v,))
+    unknown = set(v) - {"aperture", "focus", "focus_at"}
+    if unknown:
+        raise ValueError('config "lens": unknown keys %r' % (sorted(unknown),))
+    if "aperture" not in v:
+        raise ValueError('config "lens" needs "aperture"')
+    if ("focus" in v) == ("focus_at" in v):
+        raise ValueError('config "lens" needs exactly one of "focus" and "focus_at", got keys %r' % (sorted(v),))
+
+    def positive(x, what):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or not x > 0:
+            raise ValueError('config "lens": "%s" must be a finite number > 0, got %r' % (what, x))
+        return float(x)
+
+    out = {"aperture": positive(v["aperture"], "aperture"), "focus": None, "focus_at": None}
+    if "focus" in v:
+        out["focus"] = positive(v["focus"], "focus")
+    else:
+        at = v["focus_at"]
+        if (not isinstance(at, (list, tuple)) or len(at) != 2 or
+                any(isinstance(x, bool) or not isinstance(x, int) or x < 0 for x in at)):
+            raise ValueError('config "lens": "focus_at" must be a pixel [px, py], got %r' % (at,))
+        out["focus_at"] = (int(at[0]), int(at[1]))
+    return out
+
+
 def parse_environment(e):
     """The "environment" extension key of a config entry ->
     {"scale": (r, g, b), "map": path or None, "rotate": degrees}.
@@ -144,6 +179,9 @@ class Config:
         # "textures": true: the model's diffuse texture maps (OBJ vt, MTL map_Kd;
         # Renderer.set_textures); false: the materials' Kd alone, as the reference
         self.textures = parse_textures(c["textures"]) if "textures" in c else False
+        # "lens": {"aperture": R, "focus": F | "focus_at": [px, py]}: a thin-lens
+        # camera (depth of field; Renderer.render_frames' lens); None: the pinhole
+        self.lens = parse_lens(c["lens"]) if "lens" in c else None
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -188,4 +226,5 @@ class Config:
     def DENOISE(self): return self.denoise  # extension: the denoise post-pass
     def ENVIRONMENT(self): return self.environment  # extension: parse_environment's dict, or None
     def SMOOTH(self): return self.smooth  # extension: smooth shading's crease angle in degrees, or None
+    def LENS(self): return self.lens  # extension: parse_lens' dict (thin-lens camera), or None
     def TEXTURES(self): return self.textures  # extension: the model's map_Kd textures on the diffuse lobe

@@ -18,6 +18,9 @@
 //    kernel-level parity with the reference code objects.
 //  * k_generate_jittered and k_render's J form — opt-in sub-pixel jitter
 //    (antialiasing), without a reference counterpart.
+//  * k_generate_lens and the lens branch of k_render's J form (lens_ray in
+//    mcpt_lens.h) — the opt-in thin-lens camera (depth of field) on top of
+//    the jitter, without a reference counterpart.
 //  * k_render's E form and k_shade's miss branch with a scene's environment
 //    (mcpt_scene_set_environment, env_radiance in mcpt_env.h) — opt-in
 //    environment lighting, without a reference counterpart either.
@@ -59,6 +62,7 @@
 #include "mcpt_env.h"      // environment lighting: EnvView, env_radiance (shared with mcpt_env.hip)
 #include "mcpt_smooth.h"   // smooth shading: VtxNormals, shading_normal (shared with mcpt_smooth.hip)
 #include "mcpt_texture.h"  // texture maps: TexRec, texture_factor (shared with mcpt_texture.hip)
+#include "mcpt_lens.h"     // thin-lens camera: LensView, lens_ray (k_render's jittered forms and k_generate_lens)
 
 using namespace mcpt;
 
@@ -972,6 +976,7 @@ struct RenderArgs {
   const VtxNormals *vnrm;     // N launches: the scene's vertex normals, indexed like S.tris (last: every other offset is the one it was)
   TexView tex;                // textured launches: the scene's texture records, indexed like S.tris, and its texel pool (after vnrm, likewise)
   const f4 *prim_tex;         // textured launches that read A.prim: each pixel's primary-hit texture factor (k_primary_tex)
+  float lens_radius, lens_focus;  // jittered launches: the thin lens (mcpt_lens.h), radius 0: none (last, like vnrm)
 };
 
 constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193, scenebuild.cpp:125)
@@ -1113,6 +1118,13 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
     }
   }
   (void)UE;
+  // the lens follows them (J launches only, with or without a lens: radius 0
+  // is the launch-uniform "no lens" every frame start tests)
+  LensView *const UL = reinterpret_cast<LensView *>(reinterpret_cast<char *>(UE) + (E ? sizeof(LdsEnv) : 0));
+  if constexpr (J) {
+    if (threadIdx.x == 0) *UL = lens_view(A.cam, A.lens_radius, A.lens_focus);
+  }
+  (void)UL;
   __syncthreads();
 
   unsigned long long n_seg = 0, n_nodes = 0, n_tests = 0, n_bad = 0;
@@ -1141,6 +1153,12 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
     float jx = 0.0f, jy = 0.0f;
     if constexpr (J) jitter_draw(seed, jx, jy);
     gen_ray_px<J>(U->cam, cc, pixel_x(pxy), pixel_y(pxy), (uint32_t)A.W, (uint32_t)A.H, o, d, jx, jy);
+    if constexpr (J) {
+      // the thin lens, after the jitter's draws: two more, and the ray through
+      // the sample's point on the focus plane (radius 0: no lens, no draw)
+      const float lr = UL->radius;
+      if (lr > 0.0f) lens_ray(UL->h, UL->u, UL->c, lr, UL->focus, seed, o, d);
+    }
   };
   // path / traversal state (declared with the pixel state below)
   f3 rinv = (f3){0.0f, 0.0f, 0.0f};
@@ -1793,6 +1811,25 @@ __global__ void k_generate_jittered(mcpt_camera cam, uint32_t w, uint32_t h, uin
   seeds[id] = seed;
   f4 o, d;
   gen_ray_px<true>(cam, cam_const(cam, w, h), x, y, w, h, o, d, jx, jy);
+  mcpt_ray &r = rays[id];
+  *(f4 *)r.origin = o;
+  *(f4 *)r.direction = d;
+}
+// The same with the thin lens of mcpt_render_frames_lens: four draws, lens_ray
+// on the jittered ray (k_render's jittered frame start with a lens)
+__global__ void k_generate_lens(mcpt_camera cam, float radius, float focus, uint32_t w, uint32_t h, uint32_t *seeds,
+                                mcpt_ray *rays) {
+  uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= w || y >= h) return;
+  const size_t id = (size_t)y * w + x;
+  uint32_t seed = seeds[id];
+  float jx, jy;
+  jitter_draw(seed, jx, jy);
+  f4 o, d;
+  gen_ray_px<true>(cam, cam_const(cam, w, h), x, y, w, h, o, d, jx, jy);
+  const LensView L = lens_view(cam, radius, focus);
+  lens_ray(L.h, L.u, L.c, L.radius, L.focus, seed, o, d);
+  seeds[id] = seed;
   mcpt_ray &r = rays[id];
   *(f4 *)r.origin = o;
   *(f4 *)r.direction = d;
@@ -3373,7 +3410,8 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
   const size_t lds_top = (size_t)top_nodes(A.top_levels) * 7 * sizeof(f4);
   // a stack per wave; one copy of the uniforms, top levels and materials per workgroup
   // (an unlit scene's launch has the LDS it had: the environment's constants only where they are read)
-  const size_t lds_env = scene->env_on ? sizeof(LdsEnv) : 0;
+  // (and the lens of a jittered launch behind them: an unjittered launch has the LDS it had)
+  const size_t lds_env = (scene->env_on ? sizeof(LdsEnv) : 0) + (p->jitter ? sizeof(LensView) : 0);
   const size_t lds_plain = (((size_t)kWgWaves * depth_entries * 64 * sizeof(int32_t) + sizeof(LdsUniforms) + lds_top +
                              lds_mats + lds_env + 15) & ~(size_t)15) + pad;
   const size_t lds_win = (((size_t)kWgWaves * kStackWindow * 64 * sizeof(int32_t) + sizeof(LdsUniforms) + lds_top +
@@ -3574,10 +3612,27 @@ static int launch_blocks(mcpt_ctx *ctx, const mcpt_render_params *p, const Kerne
   return MCPT_OK;
 }
 
+// A lens argument's values (null: none): 0 fine, else MCPT_ERR_ARG with `who` in the message.
+static int check_lens(const mcpt_lens *lens, const char *who) {
+  if (!lens) return MCPT_OK;
+  if (!std::isfinite(lens->radius) || !std::isfinite(lens->focus_distance) || lens->radius < 0.0f ||
+      lens->focus_distance <= 0.0f)
+    return mcpt::fail(MCPT_ERR_ARG, std::string(who) + ": bad lens (radius >= 0, focus distance > 0, both finite)");
+  return MCPT_OK;
+}
+
 int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_render_params *p,
                        uint32_t *seeds, float *hist, int32_t *count, void *stream) {
+  return mcpt_render_frames_lens(ctx, scene, cam, nullptr, p, seeds, hist, count, stream);
+}
+
+int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_lens *lens,
+                            const mcpt_render_params *p, uint32_t *seeds, float *hist, int32_t *count, void *stream) {
   if (!ctx || !scene || !cam || !p || !seeds || !hist || !count) return mcpt::fail(MCPT_ERR_ARG, "render: null argument");
   MCPT_TRY(check_render(p));
+  MCPT_TRY(check_lens(lens, "render"));
+  const bool lens_on = lens && lens->radius > 0.0f;
+  if (lens_on && p->jitter != 1) return mcpt::fail(MCPT_ERR_ARG, "render: a lens needs params->jitter = 1");
   HIP_OK(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   RenderArgs A;
@@ -3586,6 +3641,7 @@ int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera
   A.env = scene->env;
   A.vnrm = scene->vnrm;
   A.tex = TexView{scene->texrec, scene->texels, scene->n_texels};
+  A.lens_radius = lens_on ? lens->radius : 0.0f, A.lens_focus = lens_on ? lens->focus_distance : 1.0f;
   A.seeds = seeds;
   A.hist = (f4 *)hist;
   A.count = count;
@@ -3670,6 +3726,19 @@ int mcpt_generate_rays_jittered(mcpt_ctx *ctx, const mcpt_camera *cam, int32_t w
   HIP_OK(hipSetDevice(ctx->device));
   hipLaunchKernelGGL(k_generate_jittered, dim3((w + 63) / 64, h), dim3(64), 0, (hipStream_t)stream, *cam, (uint32_t)w,
                      (uint32_t)h, seeds, rays);
+  HIP_OK(hipGetLastError());
+  return MCPT_OK;
+}
+
+int mcpt_generate_rays_lens(mcpt_ctx *ctx, const mcpt_camera *cam, const mcpt_lens *lens, int32_t w, int32_t h,
+                            uint32_t *seeds, mcpt_ray *rays, void *stream) {
+  if (!ctx || !cam || !seeds || !rays || w <= 0 || h <= 0)
+    return mcpt::fail(MCPT_ERR_ARG, "generate_rays_lens: bad argument");
+  MCPT_TRY(check_lens(lens, "generate_rays_lens"));
+  if (!lens || !(lens->radius > 0.0f)) return mcpt_generate_rays_jittered(ctx, cam, w, h, seeds, rays, stream);
+  HIP_OK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_generate_lens, dim3((w + 63) / 64, h), dim3(64), 0, (hipStream_t)stream, *cam, lens->radius,
+                     lens->focus_distance, (uint32_t)w, (uint32_t)h, seeds, rays);
   HIP_OK(hipGetLastError());
   return MCPT_OK;
 }

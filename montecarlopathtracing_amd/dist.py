@@ -62,7 +62,8 @@ def reduce_image(hist, count, seeds, mask, group=None, dst=0):
 
 
 def render_distributed(renderer, scene, camera, width, height, max_depth, max_attempt, frames, seeds,
-                       stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None, textures=None):
+                       stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None, textures=None,
+                       lens=None):
     """Render the whole image across the process group; rank 0 gets the image.
     `jitter`: Renderer.render_frames' sub-pixel jitter (per-pixel draws, so
     still the single-GPU image for any GPU count).  `vertex_normals`: smooth
@@ -70,7 +71,9 @@ def render_distributed(renderer, scene, camera, width, height, max_depth, max_at
     renders (Renderer.set_vertex_normals; None: the scene as it is), so every
     rank shades its stripes with the same ones.  `textures`: a (uv, tri_tex,
     images) triple (scene.load_textures'), set on this rank's scene likewise
-    (Renderer.set_textures).
+    (Renderer.set_textures).  `lens`: Renderer.render_frames' thin lens (R, F)
+    on every rank (per-pixel draws like the jitter's, which it switches on: no
+    bit depends on the striping).
     Returns (hist, count, seeds) as numpy on rank 0, None elsewhere."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if vertex_normals is not None:
@@ -78,7 +81,8 @@ def render_distributed(renderer, scene, camera, width, height, max_depth, max_at
     if textures is not None:
         renderer.set_textures(scene, *textures)
     st = renderer.new_state(width, height, seeds)
-    kw = dict(stripe_rows=stripe_rows, stripe_index=rank, stripe_count=world, mode=mode, jitter=jitter)
+    kw = dict(stripe_rows=stripe_rows, stripe_index=rank, stripe_count=world, mode=mode,
+              jitter=True if lens is not None else jitter, lens=lens)
     if frames >= 4096:  # long runs: each rank times the leaf schedules and S/fetch thresholds on one-block
         # 16-frame calls (same bits; neither block sizing nor tile order is tuned: long calls run
         # max_block_frames blocks, a regime one-block trials do not enter, App.update)

@@ -39,6 +39,26 @@ def default_seeds(n, variant="splitmix"):
     return s
 
 
+def _lens_struct(lens):
+    """(R, F) -> L.Lens, None -> None.  Values are checked by the library."""
+    if lens is None:
+        return None
+    try:
+        r, f = lens
+        return L.Lens(float(r), float(f))
+    except (TypeError, ValueError):
+        raise ValueError("lens must be (radius, focus_distance), got %r" % (lens,))
+
+
+def focus_from_hit(t, ray_direction, camera_direction):
+    """The focus distance that puts a first hit in focus: F = t * dot(d, c^),
+    the hit's distance `t` along the unit ray direction `d`, measured along the
+    view axis c^ = camera_direction / |camera_direction| (float64, host)."""
+    d = np.asarray(ray_direction, dtype=np.float64)[:3]
+    c = np.asarray(camera_direction, dtype=np.float64)[:3]
+    return float(t) * float(np.dot(d, c / np.linalg.norm(c)))
+
+
 class DeviceScene:
     """SceneBuild::buildScene result living in HBM (child-box node layout).
     `data` is a host SceneData (mcpt_scene_upload), or a tuple (tris, nodes,
@@ -253,7 +273,7 @@ class Renderer:
     # ---------------------------------------------------------- fused path
     def render_frames(self, scene, camera, state, max_depth, max_attempt, frames, frame_begin=None,
                       stripe_rows=16, stripe_index=0, stripe_count=1, mode=L.MODE_EXACT,
-                      frames_per_launch=0, schedule=None, jitter=False):
+                      frames_per_launch=0, schedule=None, jitter=None, lens=None):
         """Frames [frame_begin, frame_begin+frames) for this GPU's row stripes
         (OpenCL::update x frames + ColorOut accumulation).  `schedule`
         (L.SCHED_*; default: the scene's, see tune_schedule) only changes speed.
@@ -261,7 +281,19 @@ class Renderer:
         primary ray goes through a point of the pixel's footprint drawn from
         the pixel's seed chain instead of its corner; such a call does without
         the primary-hit cache.  True / False or 0 / 1; another integer is the
-        library's MCPT_ERR_ARG."""
+        library's MCPT_ERR_ARG.  None (the default): on with a lens, else off.
+        `lens` = (R, F) (opt-in depth of field; mcpt_render_frames_lens): a
+        thin lens of radius R focused at distance F along the view axis, in
+        scene units.  A lens needs a fresh primary ray every frame, so it
+        switches `jitter` on; jitter=False given with a lens is a ValueError.
+        R = 0 is no lens (the jittered call's bits)."""
+        lens_c = _lens_struct(lens)
+        if lens_c is not None:
+            if jitter is not None and not jitter:
+                raise ValueError("render_frames: a lens needs jitter (leave `jitter` out, or pass True)")
+            jitter = True
+        elif jitter is None:
+            jitter = False
         p = L.RenderParams()
         p.width, p.height = state.width, state.height
         p.max_depth, p.max_attempt = int(max_depth), int(max_attempt)
@@ -273,8 +305,13 @@ class Renderer:
         p.schedule = int(getattr(scene, "schedule", L.SCHED_PAIRED) if schedule is None else schedule)
         p.jitter = int(jitter)
         cam = np.ascontiguousarray(camera)
-        L.check(L.lib().mcpt_render_frames(self.ctx, scene.handle, L.ptr(cam), ctypes.byref(p), L.ptr(state.seeds),
-                                           L.ptr(state.hist), L.ptr(state.count), _stream()))
+        if lens_c is not None:
+            L.check(L.lib().mcpt_render_frames_lens(self.ctx, scene.handle, L.ptr(cam), ctypes.byref(lens_c),
+                                                    ctypes.byref(p), L.ptr(state.seeds), L.ptr(state.hist),
+                                                    L.ptr(state.count), _stream()))
+        else:
+            L.check(L.lib().mcpt_render_frames(self.ctx, scene.handle, L.ptr(cam), ctypes.byref(p), L.ptr(state.seeds),
+                                               L.ptr(state.hist), L.ptr(state.count), _stream()))
         state.frames_done = p.frame_begin + p.frames
         return state
 
@@ -283,7 +320,7 @@ class Renderer:
         `frames` frames `trials` times with each schedule on a scratch copy
         of `state` (interleaved, device time of each call), keep the faster
         in scene.schedule.  Both schedules give bit-identical images, so this
-        only moves speed.  Keywords (`jitter` among them) go to the scratch
+        only moves speed.  Keywords (`jitter` and `lens` among them) go to the scratch
         renders it times.  Returns (schedule, {schedule: best ms})."""
         sched, _, best = self.tune(scene, camera, state, max_depth, max_attempt, frames, trials, shade_thresholds=None,
                                    fetch_thresholds=None, tile_orders=None, **kw)
@@ -309,8 +346,8 @@ class Renderer:
         predict; the minimum favoured lucky runs).  fresh_view: every trial
         call first drops the primary-hit cache, so it pays the primary-hit
         pass and the tile sort as a call of a new view does (bench.py's timed
-        call).  Keywords of render_frames (mode, stripes, `jitter`) go to every
-        scratch render, so a jittered render is tuned as it will run.  The winner goes to
+        call).  Keywords of render_frames (mode, stripes, `jitter`, `lens`) go to every
+        scratch render, so a jittered or defocused render is tuned as it will run.  The winner goes to
         scene.schedule and the renderer's tuning.  Returns (schedule,
         shade_threshold, {(schedule, shade, fetch, entries, tile_order): median ms})."""
         if getattr(self, "_stats_on", False):
@@ -418,6 +455,20 @@ class Renderer:
         cam = np.ascontiguousarray(camera)
         L.check(L.lib().mcpt_generate_rays_jittered(self.ctx, L.ptr(cam), width, height, L.ptr(seeds), L.ptr(rays),
                                                     _stream()))
+        return rays
+
+    def generate_rays_lens(self, camera, width, height, seeds, lens):
+        """generate_rays_jittered plus the thin lens `lens` = (R, F) of
+        render_frames (mcpt_generate_rays_lens): four draws a pixel, the two
+        of the jitter and then the two of the lens sample.  None or R = 0: the
+        jittered call, two draws."""
+        if seeds.numel() != width * height or seeds.element_size() != 4 or not seeds.is_cuda:
+            raise L.MCPTError("generate_rays_lens: seeds must be a CUDA tensor of width*height 32-bit words")
+        rays = _dev_bytes(width * height * L.RAY.itemsize, self.device)
+        cam = np.ascontiguousarray(camera)
+        lens_c = _lens_struct(lens)
+        L.check(L.lib().mcpt_generate_rays_lens(self.ctx, L.ptr(cam), None if lens_c is None else ctypes.byref(lens_c),
+                                                width, height, L.ptr(seeds), L.ptr(rays), _stream()))
         return rays
 
     def intersect(self, scene, rays, hits=None, tmin=0.001, mode=L.MODE_EXACT):
@@ -602,6 +653,21 @@ class Renderer:
         """Every pixel's first hit (W*H Hit records, device bytes): generate_rays
         then intersect, the corner ray's also when the render is jittered."""
         return self.intersect(scene, self.generate_rays(camera, width, height), mode=mode)
+
+    def autofocus(self, scene, camera, width, height, px, py, mode=L.MODE_EXACT):
+        """The lens focus distance F that puts what pixel (px, py) sees in
+        focus: focus_from_hit of the pixel's corner ray's first hit
+        (first_hits).  A ray that hits nothing there is a ValueError."""
+        px, py = int(px), int(py)
+        if not (0 <= px < width and 0 <= py < height):
+            raise ValueError("autofocus: pixel (%d, %d) is outside the %d x %d image" % (px, py, width, height))
+        rays = self.generate_rays(camera, width, height)
+        hit = records(self.intersect(scene, rays, mode=mode), L.HIT)[py * width + px]
+        ray = records(rays, L.RAY)[py * width + px]
+        if not float(hit["t"]) < 3.0e38:
+            raise ValueError("autofocus: the ray of pixel (%d, %d) hits nothing to focus on" % (px, py))
+        cam = np.ascontiguousarray(camera).view(L.CAMERA).reshape(-1)[0]
+        return focus_from_hit(hit["t"], ray["direction"], cam["direction"])
 
     def denoise(self, scene, hits, state, iterations=None, sigma_normal=None, sigma_plane=None, sigma_color=None,
                 albedo=None):
