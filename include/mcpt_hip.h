@@ -273,7 +273,9 @@ typedef struct mcpt_tuning {
  * mcpt_load_mtl_maps, mcpt_mtl_maps_from_text, mcpt_scene_set_textures with
  * its own mcpt_textures, mcpt_texture_eval) came in at 5 likewise, and so
  * did the thin lens (mcpt_render_frames_lens and mcpt_generate_rays_lens with
- * their own mcpt_lens).
+ * their own mcpt_lens) and the normal-map entry points
+ * (mcpt_load_mtl_bump_maps, mcpt_mtl_bump_maps_from_text,
+ * mcpt_scene_set_normal_maps with its own mcpt_normal_maps, mcpt_bump_eval).
  * A binding checks mcpt_abi_version() == MCPT_ABI_VERSION once at load and
  * refuses a library built from another header.                           */
 #define MCPT_ABI_VERSION 5
@@ -785,6 +787,96 @@ int mcpt_mtl_maps_from_text(const char *text, int64_t len, char *names, int64_t 
 int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_textures *textures);
 int mcpt_texture_eval(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *tri_ids_dev, const float *points_dev,
                       int64_t n, float *out_dev, void *stream);
+
+/* Opt-in bump and normal maps (MTL `map_Bump`, `bump`, `norm`; no reference
+ * counterpart).  The reference, and a scene without maps,
+ * shade a hit with its face normal (or, with vertex normals, the interpolated
+ * one).
+ *
+ * Normative (fp32 on the device, csrc/mcpt_bump.h; float64 in
+ * tests/bump_ref.py).  A scene has a second pool of maps, each W x H
+ * tangent-space normals (mx, my, mz) as float texels, row 0 the top, every
+ * texel unit within 1e-3 with mz > 0; red is +u and green is +v, where OBJ's v
+ * points up (the "Y+" convention).  Each triangle has three UV pairs and a map
+ * index, or -1: unmapped.
+ * At set time, on the host in double, with e1 = v1 - v0, e2 = v2 - v0 (the
+ * uploaded rows), du1 = u1 - u0, dv1 = v1 - v0 and du2, dv2 likewise:
+ *   det = du1 dv2 - du2 dv1; T = (dv2 e1 - dv1 e2) / det;
+ *   B = (du1 e2 - du2 e1) / det; t = normalize(T), rounded once;
+ *   h = +1 when dot(cross(ng, T), B) >= 0, else -1 (ng: the packed face
+ *   normal); det zero or not finite, or T zero or not finite: unmapped.
+ * At a shaded hit with ray direction d, N the normal that would be shaded
+ * without maps (the ray-facing result of the smooth lookup above, or the
+ * flipped face normal):
+ *   1. m = (mx, my, mz): the barycentrics, u', v', x, y and the bilinear filter
+ *      with wrap of the texture lookup above, bit for bit (the rule that a
+ *      channel whose four texels are equal is that value exactly included),
+ *      over the normal pool;
+ *   2. an unmapped triangle gives N bit for bit after one 16-B gather; so does
+ *      mx == 0 && my == 0;
+ *   3. f = dot(N, ng) < 0 ? -1 : +1; nt = dot(N, t); tp = fma(-nt, N, t) per
+ *      component; |tp|^2 zero or not finite gives N; T' = normalize(tp);
+ *      B' = (h f) cross(N, T');
+ *   4. n = fma(mz, N, fma(my, B', mx T')) per component; |n|^2 zero or not
+ *      finite gives N; n' = normalize(n); a non-finite n' gives N; dot(n', d)
+ *      >= 0 (turned away from the viewer) gives N; n'.w keeps N.w's bits.
+ * dot, cross and normalize are those of the shading code (fma chains, one
+ * v_rsq_f32).  No random number is drawn.  n' replaces the shading normal for
+ * every material, as smooth normals do.
+ *
+ * mcpt_load_mtl_bump_maps returns, per material in mcpt_load_obj's material
+ * order, the map's file name ('\0'-terminated, back to back; empty: none), its
+ * kind (MCPT_BUMP_NORMAL for `norm`, MCPT_BUMP_HEIGHT for `map_Bump`,
+ * `map_bump` or `bump`, MCPT_BUMP_NONE) and its `-bm` value (default 1).
+ * Other options are skipped; `norm` wins over a height map whatever their
+ * order; backslashes become slashes.  Two calls: names NULL gives *n_bytes and
+ * *n_materials; otherwise *n_bytes is the name buffer's capacity and kinds and
+ * bm hold *n_materials entries on entry.  mcpt_mtl_bump_maps_from_text is the
+ * same on MTL text.
+ *
+ * mcpt_scene_set_normal_maps(ctx, scene, m): host uv (n_tris x 6) and tri_map
+ * (n_tris) in the upload's triangle order, n_maps images {xyz, width, height}
+ * of width * height * 3 floats.  Validated first: UVs of mapped triangles
+ * finite with |uv| <= 2^20, indices in [-1, n_maps), texels as above, sides in
+ * 1..16384, at most 2^27 texels in all (checked from the sizes before a texel
+ * is read); MCPT_ERR_ARG leaves the scene as it was.  Uploads float4 texels in
+ * one pool and a 48-B record per triangle (a second copy per search-tree slot
+ * in a scene that has the 96-B nodes); m NULL clears the maps.  It waits for
+ * work enqueued on the scene's GPU before it frees previous arrays and drops
+ * the context's primary-hit cache.  mcpt_scene_destroy frees the arrays.
+ *
+ * With maps set: mcpt_render_frames runs k_render's mapped forms (both modes;
+ * with or without vertex normals and textures); its primary-hit cache holds
+ * n' as the finished normal, the same bits with mcpt_tuning.primary_cache off,
+ * auto or always; mcpt_intersect writes n' to mcpt_hit.normal and reports the
+ * closest hit's triangle in both modes, as on a textured scene, so mcpt_shade
+ * and the denoiser's guide follow.
+ *
+ * mcpt_bump_eval evaluates n' for n queries on the device: tri_ids_dev int32
+ * triangle indices (upload order), points_dev, dirs_dev and normals_dev n
+ * float4 each (xyz used; normals_dev is N, .w kept), out_dev n float4.
+ * MCPT_ERR_ARG when the scene has no maps; an index outside the scene's
+ * triangles gives zeros.  Stream-ordered.                                  */
+#define MCPT_BUMP_NONE 0
+#define MCPT_BUMP_HEIGHT 1
+#define MCPT_BUMP_NORMAL 2
+typedef struct mcpt_normal_map_image {
+  const float *xyz; /* width * height * 3, row 0 the top */
+  int32_t width, height;
+} mcpt_normal_map_image;
+typedef struct mcpt_normal_maps {
+  const float *uv;          /* n_tris x 6 */
+  const int32_t *tri_map;   /* n_tris, -1: unmapped */
+  int32_t n_maps;
+  const mcpt_normal_map_image *images;
+} mcpt_normal_maps;
+int mcpt_load_mtl_bump_maps(const char *directory, const char *objname, char *names, int32_t *kinds, float *bm,
+                            int64_t *n_bytes, int64_t *n_materials);
+int mcpt_mtl_bump_maps_from_text(const char *text, int64_t len, char *names, int32_t *kinds, float *bm,
+                                 int64_t *n_bytes, int64_t *n_materials);
+int mcpt_scene_set_normal_maps(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_normal_maps *maps);
+int mcpt_bump_eval(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *tri_ids_dev, const float *points_dev,
+                   const float *dirs_dev, const float *normals_dev, int64_t n, float *out_dev, void *stream);
 
 /* Counters of the last render call (segments etc. need stats enabled);
  * waits for that call's work to finish.                                   */

@@ -3,7 +3,7 @@ or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
         [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]] [--smooth [DEG]]
-        [--textures] [--aperture R (--focus F | --focus-at X,Y)]
+        [--textures] [--bump [SCALE]] [--aperture R (--focus F | --focus-at X,Y)]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -40,6 +40,9 @@ def parser():
     ap.add_argument("--textures", action="store_true",
                     help="the model's diffuse texture maps (OBJ vt, MTL map_Kd), even if the config entry has no "
                          "\"textures\" key")
+    ap.add_argument("--bump", nargs="?", type=float, const=True, default=None, metavar="SCALE",
+                    help="the model's bump and normal maps (MTL map_Bump, bump, norm); SCALE: factor on a height "
+                         "map's per-texel slopes (default 1), even if the config entry has no \"bump\" key")
     ap.add_argument("--aperture", type=float, default=None, metavar="R",
                     help="thin-lens camera (depth of field): the lens radius in scene units; needs --focus or "
                          "--focus-at, switches --jitter on, overrides the config entry's \"lens\"")
@@ -72,6 +75,12 @@ def cli_lens(a):
     if len(at) != 2:
         raise ValueError("--focus-at: expected a pixel X,Y, got %r" % (a.focus_at,))
     return {"aperture": a.aperture, "focus_at": at}
+
+
+def cli_bump(a, cfg):
+    """The height-map scale a run maps with, or None: --bump [SCALE] if given, else the entry's "bump"."""
+    from . import config as C
+    return cfg.BUMP() if a.bump is None else C.parse_bump(a.bump)
 
 
 def cli_smooth(a, cfg):
@@ -132,7 +141,7 @@ def main(argv=None):
     from .app import App
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
               denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth,
-              textures=True if a.textures else None, lens=cli_lens(a))
+              textures=True if a.textures else None, lens=cli_lens(a), bump=a.bump)
     if app.lens_spec is not None:
         print("lens: jitter switched on (a lens needs a fresh primary ray every frame)")
     t0 = time.time()
@@ -156,7 +165,7 @@ def _main_dist(a):
     from . import dist as D
     from . import render as R
     from . import scene as S
-    from .app import apply_environment, apply_smooth, apply_textures, config_scene, resolve_lens
+    from .app import apply_bump, apply_environment, apply_smooth, apply_textures, config_scene, resolve_lens
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # MCPT_DIST_SHARED_GPU=1 rehearses the N-rank job on a one-GPU box: every
     # rank on device 0, gloo for the one reduce (tests/test_gpu_dist.py)
@@ -182,6 +191,7 @@ def _main_dist(a):
     apply_environment(rnd, sc, cfg.ENVIRONMENT() if env is None else C.parse_environment(env), cfg, root)
     apply_smooth(rnd, sc, cli_smooth(a, cfg), cfg, root)  # and shades with its own copy of the vertex normals
     textured = apply_textures(rnd, sc, a.textures or cfg.TEXTURES(), cfg, root)  # and of the textures
+    apply_bump(rnd, sc, cli_bump(a, cfg), cfg, root)  # and of the bump and normal maps
     w, h = cfg.WIDTH(), cfg.HEIGHT()
     frames = a.frames or cfg.MAXATTEPMT() + 1
     spec = cli_lens(a)

@@ -79,6 +79,17 @@ class Textures(ctypes.Structure):
                 ("images", ctypes.c_void_p)]
 
 
+class NormalMapImage(ctypes.Structure):
+    """mcpt_normal_map_image: xyz (host float32, width * height * 3), width, height."""
+    _fields_ = [("xyz", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
+
+
+class NormalMaps(ctypes.Structure):
+    """mcpt_normal_maps: uv (n_tris x 6 float32), tri_map (n_tris int32), n_maps, images."""
+    _fields_ = [("uv", ctypes.c_void_p), ("tri_map", ctypes.c_void_p), ("n_maps", ctypes.c_int32),
+                ("images", ctypes.c_void_p)]
+
+
 class Environment(ctypes.Structure):
     """mcpt_environment: scale[4], map_rgb (host float32 RGB rows, or NULL),
     width, height, rotate_deg."""
@@ -129,6 +140,10 @@ SIGNATURES = {
     "mcpt_mtl_maps_from_text": (_I32, [_P, _I64, _P, _P, _P]),
     "mcpt_scene_set_textures": (_I32, [_P, _P, _P]),
     "mcpt_texture_eval": (_I32, [_P, _P, _P, _P, _I64, _P, _P]),
+    "mcpt_load_mtl_bump_maps": (_I32, [_S, _S, _P, _P, _P, _P, _P]),
+    "mcpt_mtl_bump_maps_from_text": (_I32, [_P, _I64, _P, _P, _P, _P, _P]),
+    "mcpt_scene_set_normal_maps": (_I32, [_P, _P, _P]),
+    "mcpt_bump_eval": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _P, _P]),
     "mcpt_ctx_create": (_I32, [_I32, _P]),
     "mcpt_ctx_destroy": (_I32, [_P]),
     "mcpt_device_count": (_I32, [_P]),

@@ -40,6 +40,12 @@ coordinates, bilinear, repeating, no mip levels; Renderer.set_textures).  The
 denoise pass then filters the image divided by the first hits' texture factor
 and multiplies it back (Renderer.denoise's albedo), so the texture stays sharp.
 
+Extension: "bump": true | <scale > 0> (App(..., bump=...), --bump [SCALE])
+shades every hit with its normal perturbed by the model's normal map (MTL
+`norm`) or height map (`map_Bump`, `bump`; slopes per texel times -bm times
+the scale) at the hit's `vt` coordinates (Renderer.set_normal_maps).  The
+denoise pass's guide follows: first_hits returns the mapped normals.
+
 Extension: "lens": {"aperture": R, "focus": F} or {"aperture": R, "focus_at":
 [px, py]} (App(..., lens={...} or (R, F)), --aperture with --focus or
 --focus-at) renders through a thin lens of radius R focused at distance F
@@ -125,6 +131,25 @@ def apply_textures(renderer, scene, on, cfg, root):
     return True
 
 
+def apply_bump(renderer, scene, scale, cfg, root):
+    """Set a config entry's bump and normal maps (OBJ vt, MTL map_Bump, bump,
+    norm) on an uploaded scene when `scale` (config.parse_bump's) is not None;
+    returns whether the scene is mapped now.  App.init and every rank of the
+    multi-GPU CLI go through this."""
+    if scale is None:
+        return False
+    directory = os.path.join(root, cfg.GETDIRECTORY())
+    if not directory.endswith("/"):
+        directory += "/"
+    tris = scene.data.tris
+    mat_index = np.ascontiguousarray(tris["normal"][:, 3]).view(np.int32)  # pack_triangles put it there
+    uv, tri_map, images = S.load_bump_maps(directory, cfg.GETOBJNAME(), scene.data.mats, mat_index, scale)
+    if not (tri_map >= 0).any():
+        return False
+    renderer.set_normal_maps(scene, uv, tri_map, images)
+    return True
+
+
 def resolve_lens(renderer, scene, camera, width, height, spec):
     """A lens spec (config.parse_lens' dict, or None) -> (R, F) or None; a
     "focus_at" pixel is focused on through Renderer.autofocus.  App.init and
@@ -140,7 +165,7 @@ def resolve_lens(renderer, scene, camera, width, height, spec):
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
                  material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None,
-                 lens=None):
+                 lens=None, bump=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -173,6 +198,8 @@ class App:
             self.jitter = True
         self.lens = None  # (R, F) once init() has resolved the focus
         self.textured = False
+        self.bump = self.cfg.BUMP() if bump is None else C.parse_bump(bump)  # None: the entry's "bump" key
+        self.mapped = False
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -194,6 +221,7 @@ class App:
         apply_environment(self.renderer, self.scene, self.environment, self.cfg, self.root)
         apply_smooth(self.renderer, self.scene, self.smooth, self.cfg, self.root)
         self.textured = apply_textures(self.renderer, self.scene, self.textures, self.cfg, self.root)
+        self.mapped = apply_bump(self.renderer, self.scene, self.bump, self.cfg, self.root)
         self.state = self.renderer.new_state(self.w, self.h, self.seeds)
         self.lens = resolve_lens(self.renderer, self.scene, self.camera, self.w, self.h, self.lens_spec)
         self._init = True

@@ -116,6 +116,19 @@ def parse_lens(v):
     return out
 
 
+def parse_bump(v):
+    """The "bump" extension key of a config entry -> the slope scale of the
+    model's height maps (true: 1.0), or None (false: no bump or normal maps)."""
+    if isinstance(v, bool):
+        return 1.0 if v else None
+    if not isinstance(v, (int, float)):
+        raise ValueError('config "bump" must be true, false or a scale > 0, got %r' % (v,))
+    v = float(v)
+    if not (v > 0.0 and v < float("inf")):
+        raise ValueError('config "bump" must be a finite scale > 0, got %r' % (v,))
+    return v
+
+
 def parse_environment(e):
     """The "environment" extension key of a config entry ->
     {"scale": (r, g, b), "map": path or None, "rotate": degrees}.
@@ -179,6 +192,9 @@ class Config:
         # "textures": true: the model's diffuse texture maps (OBJ vt, MTL map_Kd;
         # Renderer.set_textures); false: the materials' Kd alone, as the reference
         self.textures = parse_textures(c["textures"]) if "textures" in c else False
+        # "bump": true | <scale > 0>: the model's bump and normal maps (MTL map_Bump,
+        # bump, norm; Renderer.set_normal_maps); None: the unmapped normals
+        self.bump = parse_bump(c["bump"]) if "bump" in c else None
         # "lens": {"aperture": R, "focus": F | "focus_at": [px, py]}: a thin-lens
         # camera (depth of field; Renderer.render_frames' lens); None: the pinhole
         self.lens = parse_lens(c["lens"]) if "lens" in c else None
@@ -228,3 +244,4 @@ class Config:
     def SMOOTH(self): return self.smooth  # extension: smooth shading's crease angle in degrees, or None
     def LENS(self): return self.lens  # extension: parse_lens' dict (thin-lens camera), or None
     def TEXTURES(self): return self.textures  # extension: the model's map_Kd textures on the diffuse lobe
+    def BUMP(self): return self.bump  # extension: the height maps' slope scale of the model's bump and normal maps, or None

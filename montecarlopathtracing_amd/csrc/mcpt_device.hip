@@ -37,6 +37,12 @@
 //    k_render's textured forms sit on the N forms and are compiled in a third
 //    translation unit (mcpt_render_texture.hip: this file with MCPT_TEXTURE_TU
 //    and the one table texture_render_fn).
+//  * k_render's mapped forms, k_primary_bump and k_intersect_bump with a scene's
+//    normal maps (mcpt_scene_set_normal_maps, bump_normal in mcpt_bump.h) —
+//    opt-in bump and normal maps, without a reference counterpart.  k_render's
+//    mapped forms sit on the textured forms and are compiled in a fourth
+//    translation unit (mcpt_render_bump.hip: this file with MCPT_BUMP_TU and
+//    the one table bump_render_fn).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -62,6 +68,7 @@
 #include "mcpt_env.h"      // environment lighting: EnvView, env_radiance (shared with mcpt_env.hip)
 #include "mcpt_smooth.h"   // smooth shading: VtxNormals, shading_normal (shared with mcpt_smooth.hip)
 #include "mcpt_texture.h"  // texture maps: TexRec, texture_factor (shared with mcpt_texture.hip)
+#include "mcpt_bump.h"     // bump and normal maps: BumpRec, bump_normal (shared with mcpt_bump.hip)
 #include "mcpt_lens.h"     // thin-lens camera: LensView, lens_ray (k_render's jittered forms and k_generate_lens)
 
 using namespace mcpt;
@@ -212,6 +219,13 @@ struct mcpt_scene {
   TexRec *texrec = nullptr, *texrec4 = nullptr;
   f4 *texels = nullptr;
   int64_t n_texels = 0;
+  // mcpt_scene_set_normal_maps: bump and normal maps.  bumprec in the order of
+  // tris and triq, bumprec4 in tri4's, bump_texels the one pool all records
+  // point into; all null: the shading normal is the unmapped one, by the
+  // kernels that never look.  A set or clear bumps vn_epoch too.
+  BumpRec *bumprec = nullptr, *bumprec4 = nullptr;
+  f4 *bump_texels = nullptr;
+  int64_t n_bump_texels = 0;
 };
 
 constexpr int kQueues = 8;         // k_render work queues (at most): one per XCD (MI355X has 8)
@@ -231,6 +245,7 @@ constexpr int64_t kPrimSmallTree = 1ll << 20;
 constexpr int kPhaseSlot = 16;     // MCPT_PHASE_TIMING: shader-clock ticks per phase (fetch, T, L, S)
 constexpr int kDebugSlot = 12;     // MCPT_DEBUG: violations of the stack bound, node, triangle and environment-texel indices
 constexpr int kTexDebugSlot = 20;  // MCPT_DEBUG: violations of the texture-record and texture-texel indices
+constexpr int kBumpDebugSlot = 21; // MCPT_DEBUG: violations of the normal-map record and texel indices
 constexpr int kWaveLogWords = 8;   // MCPT_PHASE_TIMING wave log (mcpt_get_wave_log)
 
 // -DMCPT_DEBUG (make debug -> lib/libmcpt_hip_debug.so): k_render checks every
@@ -977,6 +992,7 @@ struct RenderArgs {
   TexView tex;                // textured launches: the scene's texture records, indexed like S.tris, and its texel pool (after vnrm, likewise)
   const f4 *prim_tex;         // textured launches that read A.prim: each pixel's primary-hit texture factor (k_primary_tex)
   float lens_radius, lens_focus;  // jittered launches: the thin lens (mcpt_lens.h), radius 0: none (last, like vnrm)
+  BumpView bump;              // mapped launches: the scene's normal-map records, indexed like S.tris, and their texel pool (last, likewise)
 };
 
 constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193, scenebuild.cpp:125)
@@ -1033,8 +1049,14 @@ constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193,
 // hit of a textured scene (k_primary_tex) holds the finished normal and the
 // material like a smooth scene's, and its factor sits in A.prim_tex: the
 // primary hit, and so its texel, is the same every frame.
+// BM: the scene has normal maps (mcpt_scene_set_normal_maps): the shading
+// normal is bump_normal (mcpt_bump.h) of the one above, at the start of the S
+// phase, after the texture factor is finished.  On top of the textured forms;
+// A.tex.rec may then be null (a mapped scene without textures: a uniform test,
+// and a factor of ones) like A.vnrm.  A cached primary hit of a mapped scene
+// (k_primary_bump) holds the mapped normal already.
 template <int MODE, bool STATS, bool WIN, bool PAIR, int FMT, bool PRIM = false, bool G = true, bool J = false,
-          bool E = false, bool N = false, bool TX = false>
+          bool E = false, bool N = false, bool TX = false, bool BM = false>
 __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(RenderArgs A) {
   constexpr bool PRUNE = MODE != MCPT_MODE_NOPRUNE;
   constexpr bool LIT = MODE == MCPT_MODE_NOPRUNE;
@@ -1042,6 +1064,7 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
   static_assert(!(X && (LIT || PRIM)), "the 96-B nodes are the EXACT shading forms'");
   static_assert(!(N && PRIM), "a smooth scene's primary-hit pass is k_primary's N form");
   static_assert(!TX || N, "the textured forms sit on the N forms, which carry the triangle index");
+  static_assert(!BM || TX, "the mapped forms sit on the textured forms, which hold the triangle's rows");
   constexpr int TQ = X ? 6 : 7;  // 16-B quads of a top-level node in LDS
   static_assert(!(J && PRIM), "the primary-hit pass is the unjittered frame start's");
   static_assert(!(E && PRIM), "the primary-hit pass records hits, not radiance");
@@ -1617,7 +1640,12 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
                 } else if (cl_dot3(d.xyz, in.nrm.xyz) > 0) {
                   in.nrm = -in.nrm;  // intersect.cl:23-25
                 }
-                tex = texture_factor<kDebug>(A.tex, ti, r0, r1, r2, in.pt, &A.stats[kTexDebugSlot]);
+                if constexpr (BM) {
+                  if (A.tex.rec) tex = texture_factor<kDebug>(A.tex, ti, r0, r1, r2, in.pt, &A.stats[kTexDebugSlot]);
+                  in.nrm = bump_normal<kDebug>(A.bump, ti, r0, r1, r2, tn.xyz, in.pt, d, in.nrm, &A.stats[kBumpDebugSlot]);
+                } else {
+                  tex = texture_factor<kDebug>(A.tex, ti, r0, r1, r2, in.pt, &A.stats[kTexDebugSlot]);
+                }
               } else if constexpr (Q) {
                 const DevTriQ &T = S.triq[ti];
                 const f4 v0 = T.v0, v1 = T.v1, v2 = T.v2;
@@ -1755,7 +1783,27 @@ const void *smooth_render_fn(int kind, int stats, int win, int pair, int jitter,
 // build of this file (mcpt_render_texture.hip) and reached through this table
 // alone: the same indices.
 const void *texture_render_fn(int kind, int stats, int win, int pair, int jitter, int env);
-#if defined(MCPT_TEXTURE_TU)
+// k_render's mapped forms (on the textured forms), compiled in the
+// MCPT_BUMP_TU build of this file (mcpt_render_bump.hip) and reached through
+// this table alone: the same indices.
+const void *bump_render_fn(int kind, int stats, int win, int pair, int jitter, int env);
+#if defined(MCPT_BUMP_TU)
+const void *bump_render_fn(int kind, int stats, int win, int pair, int jitter, int env) {
+#define MCPT_NE(M, ST, W, P, QN, J) {(const void *)k_render<M, ST, W, P, QN, false, true, J, false, true, true, true>, \
+                                     (const void *)k_render<M, ST, W, P, QN, false, true, J, true, true, true, true>}
+#define MCPT_NJ(M, ST, W, P, QN) {MCPT_NE(M, ST, W, P, QN, false), MCPT_NE(M, ST, W, P, QN, true)}
+#define MCPT_NW(M, ST, W, QN) {MCPT_NJ(M, ST, W, false, QN), MCPT_NJ(M, ST, W, true, QN)}
+#define MCPT_NK(M, QN) {{MCPT_NW(M, false, false, QN), MCPT_NW(M, false, true, QN)}, \
+                        {MCPT_NW(M, true, false, QN), MCPT_NW(M, true, true, QN)}}
+  static const void *const fns[4][2][2][2][2][2] = {MCPT_NK(MCPT_MODE_EXACT, kFmt128), MCPT_NK(MCPT_MODE_NOPRUNE, kFmt128),
+                                                    MCPT_NK(MCPT_MODE_EXACT, kFmtQ), MCPT_NK(MCPT_MODE_EXACT, kFmt96)};
+#undef MCPT_NK
+#undef MCPT_NW
+#undef MCPT_NJ
+#undef MCPT_NE
+  return fns[kind & 3][stats & 1][win & 1][pair & 1][jitter & 1][env & 1];
+}
+#elif defined(MCPT_TEXTURE_TU)
 const void *texture_render_fn(int kind, int stats, int win, int pair, int jitter, int env) {
 #define MCPT_NE(M, ST, W, P, QN, J) {(const void *)k_render<M, ST, W, P, QN, false, true, J, false, true, true>, \
                                      (const void *)k_render<M, ST, W, P, QN, false, true, J, true, true, true>}
@@ -1844,9 +1892,11 @@ __global__ void k_generate_lens(mcpt_camera cam, float radius, float focus, uint
 // NOPRUNE too (the reference's field is the last accepted one, which names
 // another triangle wherever the ray passes through more than one), so k_shade_tex
 // looks the texture up on the triangle the hit's point lies on; vnrm may be null.
-template <int MODE, bool N, bool TXI = false>
+// BMI (on TXI): the scene has normal maps: the hit's normal is bump_normal of
+// the one above, so k_shade and k_shade_tex follow without a change.
+template <int MODE, bool N, bool TXI = false, bool BMI = false>
 __device__ __forceinline__ void intersect_one(const SceneView &S, const mcpt_ray *rays, int64_t n, mcpt_hit *hits,
-                                              float tmin, const VtxNormals *vnrm) {
+                                              float tmin, const VtxNormals *vnrm, const BumpView &bump = BumpView{}) {
   extern __shared__ int32_t lds_stack[];
   int64_t id = (int64_t)blockIdx.x * 64 + threadIdx.x;
   if (id >= n) return;
@@ -1886,6 +1936,13 @@ __device__ __forceinline__ void intersect_one(const SceneView &S, const mcpt_ray
       } else if (cl_dot3(d.xyz, nrm.xyz) > 0) {
         nrm = -nrm;
       }
+      if constexpr (BMI) {
+        if (tr.tri >= 0) {
+          const DevTri &T = S.tris[tr.tri];
+          const f4 v0 = T.v0, nab = T.nab, nac = T.nac;
+          nrm = bump_normal(bump, tr.tri, v0.xyz, nab.xyz, nac.xyz, (f3){v0.w, nab.w, nac.w}, pt, d, nrm);
+        }
+      }
     } else if constexpr (N) {
       if (tr.tri >= 0) {
         const DevTri &T = S.tris[tr.tri];
@@ -1915,6 +1972,11 @@ __global__ void __launch_bounds__(64) k_intersect_tex(SceneView S, const mcpt_ra
                                                       float tmin, const VtxNormals *vnrm) {
   intersect_one<MODE, true, true>(S, rays, n, hits, tmin, vnrm);
 }
+template <int MODE>
+__global__ void __launch_bounds__(64) k_intersect_bump(SceneView S, const mcpt_ray *rays, int64_t n, mcpt_hit *hits,
+                                                       float tmin, const VtxNormals *vnrm, BumpView bump) {
+  intersect_one<MODE, true, true, true>(S, rays, n, hits, tmin, vnrm, bump);
+}
 
 // The primary hit of every pixel of this rank's stripes (the cache k_render
 // reads at each frame start, PrimHit): the frame's first ray (gen_ray_px, as
@@ -1926,7 +1988,9 @@ __global__ void __launch_bounds__(64) k_intersect_tex(SceneView S, const mcpt_ra
 // TX (k_primary_tex): the scene has textures: the record holds the finished
 // normal (the shading normal, or without vertex normals the flipped face
 // normal) and the hit's texture factor goes to tex_out, 16 B per pixel.
-template <int MODE, bool N, bool TX>
+// BM (k_primary_bump, on TX): the scene has normal maps: the finished normal
+// is bump_normal of that one; A.tex.rec may be null (a factor of ones).
+template <int MODE, bool N, bool TX, bool BM = false>
 __device__ __forceinline__ void primary_one(const RenderArgs &A, PrimHit *out, f4 *tex_out) {
   extern __shared__ int32_t lds_stack[];
   // one 8x8 tile of the rank's rows per wave: neighbouring primary rays walk
@@ -1957,8 +2021,13 @@ __device__ __forceinline__ void primary_one(const RenderArgs &A, PrimHit *out, f
       } else if (cl_dot3(d.xyz, ns.xyz) > 0) {
         ns = -ns;  // intersect.cl:23-25
       }
+      if constexpr (BM) {
+        if (A.tex.rec) tex = texture_factor(A.tex, tr.tri, v0.xyz, nab.xyz, nac.xyz, pt);
+        ns = bump_normal(A.bump, tr.tri, v0.xyz, nab.xyz, nac.xyz, h.nrm.xyz, pt, d, ns);
+      } else {
+        tex = texture_factor(A.tex, tr.tri, v0.xyz, nab.xyz, nac.xyz, pt);
+      }
       h.nrm = (f4){ns.x, ns.y, ns.z, T.aux.x};
-      tex = texture_factor(A.tex, tr.tri, v0.xyz, nab.xyz, nac.xyz, pt);
     } else if constexpr (N) {
       const f4 v0 = T.v0, nab = T.nab, nac = T.nac;
       const f4 ns = shading_normal(A.vnrm, tr.tri, v0.xyz, nab.xyz, nac.xyz, h.nrm.xyz, o + tr.t * d, d);
@@ -1979,6 +2048,10 @@ __global__ void __launch_bounds__(64) k_primary(RenderArgs A, PrimHit *out) {
 template <int MODE>
 __global__ void __launch_bounds__(64) k_primary_tex(RenderArgs A, PrimHit *out, f4 *tex_out) {
   primary_one<MODE, true, true>(A, out, tex_out);
+}
+template <int MODE>
+__global__ void __launch_bounds__(64) k_primary_bump(RenderArgs A, PrimHit *out, f4 *tex_out) {
+  primary_one<MODE, true, true, true>(A, out, tex_out);
 }
 
 // The dearest-first tile order (mcpt_tuning.tile_order): each 8x8 tile of
@@ -2382,7 +2455,8 @@ int mcpt_get_stats(mcpt_ctx *c, mcpt_stats *out) {
       c->last.lane_waiting = h[9];
       c->last.lane_idle = h[10];
       c->last.leaf_rejects = h[11];
-      c->last.debug_violations = h[kDebugSlot] + h[kDebugSlot + 1] + h[kDebugSlot + 2] + h[kDebugSlot + 3] + h[kTexDebugSlot];
+      c->last.debug_violations = h[kDebugSlot] + h[kDebugSlot + 1] + h[kDebugSlot + 2] + h[kDebugSlot + 3] + h[kTexDebugSlot] +
+                                 h[kBumpDebugSlot];
       for (int k = 0; k < 4; ++k) c->last.phase_ticks[k] = h[kPhaseSlot + k];
     }
   }
@@ -3004,7 +3078,7 @@ int mcpt_scene_destroy(mcpt_scene *s) {
   for (void *p : {(void *)s->nodes, (void *)s->nodes4, (void *)s->near4, (void *)s->tris, (void *)s->near4q,
                   (void *)s->triq, (void *)s->mats, (void *)s->env_map, (void *)s->near4x, (void *)s->nodes4x,
                   (void *)s->tri4, (void *)s->vnrm, (void *)s->vnrm4, (void *)s->texrec, (void *)s->texrec4,
-                  (void *)s->texels})
+                  (void *)s->texels, (void *)s->bumprec, (void *)s->bumprec4, (void *)s->bump_texels})
     if (p) (void)hipFree(p);
   delete s;
   return MCPT_OK;
@@ -3340,6 +3414,143 @@ int texture_scene(const mcpt_scene *scene, TextureScene *out, int *on, int *devi
 }  // namespace mcpt
 }  // extern "C++"
 
+// tri4-ordered normal-map records from the reference-ordered ones
+// (k_texrec_relabel's rule): an empty slot or a foreign id gets the unmapped record
+__global__ void __launch_bounds__(256) k_bumprec_relabel(const DevTri *__restrict__ tri4, int64_t n4, int64_t n_tris,
+                                                         const BumpRec *__restrict__ rec, BumpRec *__restrict__ rec4) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n4) return;
+  const int64_t t = (int64_t)mcpt::n96_bits(tri4[k].aux.y);
+  BumpRec r;
+  r.q[0] = r.q[1] = r.q[2] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+  if (t < n_tris) r = rec[t];
+  rec4[k] = r;
+}
+
+int mcpt_scene_set_normal_maps(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_normal_maps *nm) {
+  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: null context or scene");
+  if (ctx->device != scene->device)
+    return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: scene and context are on different GPUs");
+  HIP_OK(hipSetDevice(scene->device));
+  const int64_t n = scene->n_tris;
+  // validate everything before anything changes: a failed call leaves the scene's maps as they were
+  std::vector<BumpRec> rec;
+  std::vector<f4> pool;
+  if (nm) {
+    if (!nm->uv || !nm->tri_map || nm->n_maps < 0 || (nm->n_maps > 0 && !nm->images))
+      return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: null uv, tri_map or images");
+    std::vector<int64_t> base((size_t)nm->n_maps);
+    int64_t total = 0;
+    for (int32_t k = 0; k < nm->n_maps; ++k) {  // the sizes alone, before a texel is read
+      const mcpt_normal_map_image &im = nm->images[k];
+      if (!im.xyz || im.width < 1 || im.width > 16384 || im.height < 1 || im.height > 16384)
+        return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: map " + std::to_string(k) + " has no texels or a side outside 1..16384");
+      base[(size_t)k] = total;
+      total += (int64_t)im.width * im.height;
+      if (total > (1ll << 27)) return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: more than 2^27 texels in all");
+    }
+    for (int64_t i = 0; i < n; ++i) {
+      const int32_t t = nm->tri_map[i];
+      if (t < -1 || t >= nm->n_maps)
+        return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: map index out of range (triangle " + std::to_string(i) + ")");
+      for (int k = 0; k < 6 && t >= 0; ++k)
+        if (!(std::fabs(nm->uv[6 * i + k]) <= 1048576.0f))
+          return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: a texture coordinate is not finite or beyond 2^20 (triangle " +
+                                              std::to_string(i) + ")");
+    }
+    pool.resize((size_t)std::max<int64_t>(total, 1));
+    pool[0] = (f4){0.0f, 0.0f, 1.0f, 0.0f};
+    for (int32_t k = 0; k < nm->n_maps; ++k) {
+      const mcpt_normal_map_image &im = nm->images[k];
+      const int64_t m = (int64_t)im.width * im.height;
+      for (int64_t j = 0; j < m; ++j) {
+        const float x = im.xyz[3 * j], y = im.xyz[3 * j + 1], z = im.xyz[3 * j + 2];
+        const double len = std::sqrt((double)x * x + (double)y * y + (double)z * z);
+        if (!(std::fabs(len - 1.0) <= 1e-3 && z > 0.0f))
+          return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: map " + std::to_string(k) + " has a texel that is not unit or has z <= 0");
+        pool[(size_t)(base[(size_t)k] + j)] = (f4){x, y, z, 0.0f};
+      }
+    }
+    // the tangent frame per triangle, in double from the uploaded rows (v0, nab
+    // = -(v1 - v0), nac = -(v2 - v0), the packed face normal in their .w lanes)
+    std::vector<DevTri> tris((size_t)n);
+    if (n > 0) HIP_OK(hipMemcpy(tris.data(), scene->tris, (size_t)n * sizeof(DevTri), hipMemcpyDeviceToHost));
+    rec.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      BumpRec &r = rec[(size_t)i];
+      r.q[0] = r.q[1] = r.q[2] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+      const int32_t t = nm->tri_map[i];
+      if (t < 0) continue;
+      const mcpt_normal_map_image &im = nm->images[t];
+      const float *u = nm->uv + 6 * i;
+      const DevTri &T = tris[(size_t)i];
+      const double e1[3] = {-(double)T.nab.x, -(double)T.nab.y, -(double)T.nab.z};
+      const double e2[3] = {-(double)T.nac.x, -(double)T.nac.y, -(double)T.nac.z};
+      const double ng[3] = {T.v0.w, T.nab.w, T.nac.w};
+      const double du1 = (double)u[2] - u[0], dv1 = (double)u[3] - u[1];
+      const double du2 = (double)u[4] - u[0], dv2 = (double)u[5] - u[1];
+      const double det = du1 * dv2 - du2 * dv1;
+      if (!(det != 0.0 && std::isfinite(det))) continue;  // degenerate UVs: unmapped
+      double Tn[3], Bn[3];
+      for (int k = 0; k < 3; ++k) Tn[k] = (dv2 * e1[k] - dv1 * e2[k]) / det, Bn[k] = (du1 * e2[k] - du2 * e1[k]) / det;
+      const double tl = std::sqrt(Tn[0] * Tn[0] + Tn[1] * Tn[1] + Tn[2] * Tn[2]);
+      if (!(tl > 0.0 && std::isfinite(tl))) continue;
+      const double c[3] = {ng[1] * Tn[2] - ng[2] * Tn[1], ng[2] * Tn[0] - ng[0] * Tn[2], ng[0] * Tn[1] - ng[1] * Tn[0]};
+      const float h = c[0] * Bn[0] + c[1] * Bn[1] + c[2] * Bn[2] >= 0.0 ? 1.0f : -1.0f;
+      const uint32_t off = (uint32_t)base[(size_t)t], size = (uint32_t)im.width | ((uint32_t)im.height << 16);
+      r.q[0] = (f4){__builtin_bit_cast(float, off), __builtin_bit_cast(float, size), u[0], u[1]};
+      r.q[1] = (f4){u[2], u[3], u[4], u[5]};
+      r.q[2] = (f4){(float)(Tn[0] / tl), (float)(Tn[1] / tl), (float)(Tn[2] / tl), h};
+    }
+  }
+  // renders already enqueued may still read the previous arrays: wait for them
+  if (scene->bumprec) HIP_OK(hipDeviceSynchronize());
+  BumpRec *a = nullptr, *a4 = nullptr;
+  f4 *px = nullptr;
+  if (nm) {
+    auto undo = [&](const std::string &what, hipError_t e) {
+      for (void *p : {(void *)a, (void *)a4, (void *)px})
+        if (p) (void)hipFree(p);
+      return mcpt::fail(MCPT_ERR_HIP, "set_normal_maps: " + what + ": " + hipGetErrorString(e));
+    };
+    hipError_t e = hipMalloc((void **)&a, (size_t)std::max<int64_t>(n, 1) * sizeof(BumpRec));
+    if (e != hipSuccess) return a = nullptr, undo("allocation", e);
+    e = hipMemcpy(a, rec.data(), (size_t)n * sizeof(BumpRec), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return undo("upload", e);
+    e = hipMalloc((void **)&px, pool.size() * sizeof(f4));
+    if (e != hipSuccess) return px = nullptr, undo("allocation", e);
+    e = hipMemcpy(px, pool.data(), pool.size() * sizeof(f4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return undo("upload", e);
+    if (scene->tri4) {
+      const int64_t n4 = 4 * (int64_t)scene->view.n_near4;
+      e = hipMalloc((void **)&a4, (size_t)n4 * sizeof(BumpRec));
+      if (e != hipSuccess) return a4 = nullptr, undo("allocation", e);
+      hipLaunchKernelGGL(k_bumprec_relabel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, scene->tri4, n4, n, a, a4);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+      if (e != hipSuccess) return undo("relabel", e);
+    }
+  }
+  for (void *p : {(void *)scene->bumprec, (void *)scene->bumprec4, (void *)scene->bump_texels})
+    if (p) (void)hipFree(p);
+  scene->bumprec = a, scene->bumprec4 = a4, scene->bump_texels = px, scene->n_bump_texels = nm ? (int64_t)pool.size() : 0;
+  ++scene->vn_epoch;  // the primary-hit records of any context are those of another scene now
+  ctx->prim_valid = false;
+  return MCPT_OK;
+}
+
+// mcpt_bump.hip reaches a scene's normal maps through this one (mcpt_bump.h)
+extern "C++" {
+namespace mcpt {
+int bump_scene(const mcpt_scene *scene, BumpScene *out, int *on, int *device) {
+  out->tris = reinterpret_cast<const f4 *>(scene->tris), out->n_tris = scene->n_tris;
+  out->bump = BumpView{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
+  *on = scene->bumprec ? 1 : 0, *device = scene->device;
+  return MCPT_OK;
+}
+}  // namespace mcpt
+}  // extern "C++"
+
 // The k_render instantiation of a render call and what it runs with.
 struct KernelChoice {
   const void *fn, *prim_fn;  // prim_fn: its PRIM form (the primary-hit pass of large trees), no stats
@@ -3419,8 +3630,11 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
   const void *const(*fns)[2][2] = kfns[scene->env_on ? 1 : 0][p->jitter][kind][ctx->stats_on];  // [window][pair][glossy]
   // a scene with vertex normals: the N forms (smooth_render_fn), one shading form for any materials
   // a scene with textures: the textured forms on top of them (texture_render_fn), vertex normals or not
-  const bool smooth = scene->vnrm != nullptr, textured = scene->texrec != nullptr;
+  // a scene with normal maps: the mapped forms on top of those (bump_render_fn), textures or not
+  const bool smooth = scene->vnrm != nullptr, textured = scene->texrec != nullptr, mapped = scene->bumprec != nullptr;
   auto fn_of = [&](int win_) {
+    if (mapped)
+      return bump_render_fn(kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0);
     if (textured)
       return texture_render_fn(kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0);
     return smooth ? smooth_render_fn(kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0)
@@ -3496,15 +3710,19 @@ static int primary_pass(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rende
   // the pass writes its own stripes' costs only: zero the others, so
   // the tile keys and mcpt_get_primary_cost never read stale words
   if (p->stripe_count > 1) HIP_OK(hipMemsetAsync(ctx->d_prim_cost, 0, (size_t)n_px * sizeof(uint32_t), st));
-  if (scene->texrec) MCPT_TRY(grow_dev(ctx->prim_tex_cap, n_px, (void **)&ctx->d_prim_tex, sizeof(f4)));
-  if (scene->near4_bytes <= kPrimSmallTree || scene->vnrm || scene->texrec) {
+  if (scene->texrec || scene->bumprec) MCPT_TRY(grow_dev(ctx->prim_tex_cap, n_px, (void **)&ctx->d_prim_tex, sizeof(f4)));
+  if (scene->near4_bytes <= kPrimSmallTree || scene->vnrm || scene->texrec || scene->bumprec) {
     // small trees: one ray per lane, one 8x8 tile per workgroup; a scene with
     // vertex normals or textures at any size (the records then hold shading
     // normals and come with texture factors, which k_render's PRIM form does
     // not compute)
     const size_t lds_p = (size_t)K.depth_entries * 64 * sizeof(int32_t);
     const dim3 g((unsigned)P.tiles);
-    if (scene->texrec && p->mode == MCPT_MODE_NOPRUNE)
+    if (scene->bumprec && p->mode == MCPT_MODE_NOPRUNE)  // normal maps: the record holds the mapped normal
+      hipLaunchKernelGGL(k_primary_bump<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
+    else if (scene->bumprec)
+      hipLaunchKernelGGL(k_primary_bump<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
+    else if (scene->texrec && p->mode == MCPT_MODE_NOPRUNE)
       hipLaunchKernelGGL(k_primary_tex<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
     else if (scene->texrec)
       hipLaunchKernelGGL(k_primary_tex<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
@@ -3579,7 +3797,7 @@ static int primary_cache(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_came
     ctx->prim_valid = true;
   }
   A.prim = ctx->d_prim;
-  A.prim_tex = scene->texrec ? ctx->d_prim_tex : nullptr;  // (the key's epoch: these are this scene's textures' factors)
+  A.prim_tex = scene->texrec || scene->bumprec ? ctx->d_prim_tex : nullptr;  // (the key's epoch: these are this scene's textures' factors)
   *state = have ? 1 : 2;
   return tile_order(ctx, P.tiles, !have, st, A);
 }
@@ -3641,6 +3859,7 @@ int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_c
   A.env = scene->env;
   A.vnrm = scene->vnrm;
   A.tex = TexView{scene->texrec, scene->texels, scene->n_texels};
+  A.bump = BumpView{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
   A.lens_radius = lens_on ? lens->radius : 0.0f, A.lens_focus = lens_on ? lens->focus_distance : 1.0f;
   A.seeds = seeds;
   A.hist = (f4 *)hist;
@@ -3695,6 +3914,7 @@ int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_c
     A.S.n_tris = 4 * (int64_t)scene->view.n_near4;
     A.vnrm = scene->vnrm4;
     A.tex.rec = scene->texrec4;
+    A.bump.rec = scene->bumprec4;
     if (A.S.root_leaf >= 0) A.S.root_leaf = 0;
   }
   MCPT_TRY(launch_blocks(ctx, p, K, P, st, A, &launches));
@@ -3752,7 +3972,14 @@ int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays,
   size_t lds = (size_t)(mode == MCPT_MODE_NOPRUNE ? scene->stack_depth : std::max(scene->stack_depth, scene->stack_depth4)) *
                64 * sizeof(int32_t);
   dim3 g((unsigned)((n + 63) / 64));
-  if (scene->texrec && mode == MCPT_MODE_NOPRUNE)  // textures: triangle_id is the closest hit's triangle
+  const BumpView bv{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
+  if (scene->bumprec && mode == MCPT_MODE_NOPRUNE)  // normal maps: mcpt_hit.normal is the mapped normal
+    hipLaunchKernelGGL(k_intersect_bump<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
+                       hits, tmin, scene->vnrm, bv);
+  else if (scene->bumprec)
+    hipLaunchKernelGGL(k_intersect_bump<MCPT_MODE_EXACT>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
+                       hits, tmin, scene->vnrm, bv);
+  else if (scene->texrec && mode == MCPT_MODE_NOPRUNE)  // textures: triangle_id is the closest hit's triangle
     hipLaunchKernelGGL(k_intersect_tex<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
                        hits, tmin, scene->vnrm);
   else if (scene->texrec)
@@ -3813,4 +4040,4 @@ int mcpt_gamma_preview(mcpt_ctx *ctx, const float *color, float *out, int64_t n,
 }
 
 }  // extern "C"
-#endif  // MCPT_TEXTURE_TU, MCPT_SMOOTH_TU
+#endif  // MCPT_BUMP_TU, MCPT_TEXTURE_TU, MCPT_SMOOTH_TU

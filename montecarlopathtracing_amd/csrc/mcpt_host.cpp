@@ -1064,8 +1064,10 @@ bool whole_number(const char *p, const char *e) {
 }
 
 // The file name of a map_Kd line's arguments [q, eol): options first (skipped,
-// not honoured), then the name, which may hold spaces; backslashes become slashes
-std::string map_name(const char *q, const char *eol) {
+// not honoured), then the name, which may hold spaces; backslashes become slashes.
+// bm: where the value of a usable `-bm` option goes (the bump multiplier of
+// map_Bump, bump and norm lines), wherever among the options it stands
+std::string map_name(const char *q, const char *eol, double *bm = nullptr) {
   static const char *const one[] = {"-blendu", "-blendv", "-clamp", "-cc", "-imfchan", "-type", "-texres", "-boost", "-bm"};
   for (;;) {
     while (q < eol && (*q == ' ' || *q == '\t')) ++q;
@@ -1077,6 +1079,12 @@ std::string map_name(const char *q, const char *eol) {
     for (const char *o : one)
       if (k == o) fixed = 1;
     if (k == "-mm") fixed = 2;
+    if (bm && k == "-bm") {
+      Tok n = next_token(q, eol);
+      double v = 0.0;
+      if (n.e - n.p < 64 && parse_number(n.p, n.e, &v) && std::isfinite(v)) *bm = v;
+      continue;
+    }
     if (fixed >= 0) {
       for (int a = 0; a < fixed; ++a) (void)next_token(q, eol);
       continue;
@@ -1250,4 +1258,97 @@ extern "C" int mcpt_load_mtl_maps(const char *directory, const char *objname, ch
     p = eol + 1;
   }
   return emit_maps(maps, names, n_bytes, n_materials);
+}
+
+// ------------------------------------------- bump and normal maps (opt-in)
+namespace {
+
+struct BumpMap {
+  std::string name;
+  int32_t kind = MCPT_BUMP_NONE;
+  double bm = 1.0;
+};
+
+// parse_mtl's records, their norm / map_Bump / map_bump / bump lines alone (one
+// per newmtl): `norm` wins over a height map whatever their order
+void parse_mtl_bump_maps(const char *p, const char *end, std::vector<BumpMap> *maps) {
+  bool have = false;
+  while (p < end) {
+    const char *eol = (const char *)std::memchr(p, '\n', end - p);
+    if (!eol) eol = end;
+    const char *q = p;
+    Tok key = next_token(q, eol);
+    const std::string k(key.p, key.e);
+    if (k == "newmtl") {
+      maps->push_back(BumpMap());
+      have = true;
+    } else if (have && (k == "norm" || k == "map_Bump" || k == "map_bump" || k == "bump")) {
+      const int32_t kind = k == "norm" ? MCPT_BUMP_NORMAL : MCPT_BUMP_HEIGHT;
+      BumpMap &m = maps->back();
+      if (kind >= m.kind || m.name.empty()) {
+        double bm = 1.0;
+        const std::string name = map_name(q, eol, &bm);
+        if (!name.empty()) m.name = name, m.kind = kind, m.bm = bm;
+      }
+    }
+    p = eol + 1;
+  }
+}
+
+int emit_bump_maps(const std::vector<BumpMap> &maps, char *names, int32_t *kinds, float *bm, int64_t *n_bytes,
+                   int64_t *n_materials) {
+  std::vector<std::string> ns;
+  for (const BumpMap &m : maps) ns.push_back(m.name);
+  if (names) {
+    if (!kinds || !bm) return fail(MCPT_ERR_ARG, "mtl_bump_maps: names, kinds and bm come together");
+    if (*n_materials < (int64_t)maps.size()) return fail(MCPT_ERR_ARG, "mtl_bump_maps: kinds and bm too small");
+  }
+  const int rc = emit_maps(ns, names, n_bytes, n_materials);
+  if (rc != MCPT_OK) return rc;
+  if (names)
+    for (size_t i = 0; i < maps.size(); ++i) {
+      const bool on = std::strlen(maps[i].name.c_str()) > 0;
+      kinds[i] = on ? maps[i].kind : MCPT_BUMP_NONE;
+      bm[i] = on ? (float)maps[i].bm : 1.0f;
+    }
+  return MCPT_OK;
+}
+
+}  // namespace
+
+extern "C" int mcpt_mtl_bump_maps_from_text(const char *text, int64_t len, char *names, int32_t *kinds, float *bm,
+                                            int64_t *n_bytes, int64_t *n_materials) {
+  if (!n_bytes || !n_materials || len < 0 || (len > 0 && !text)) return fail(MCPT_ERR_ARG, "mtl_bump_maps: bad argument");
+  std::vector<BumpMap> maps;
+  parse_mtl_bump_maps(text, text + len, &maps);
+  return emit_bump_maps(maps, names, kinds, bm, n_bytes, n_materials);
+}
+
+extern "C" int mcpt_load_mtl_bump_maps(const char *directory, const char *objname, char *names, int32_t *kinds, float *bm,
+                                       int64_t *n_bytes, int64_t *n_materials) {
+  if (!directory || !objname || !n_bytes || !n_materials) return fail(MCPT_ERR_ARG, "load_mtl_bump_maps: null argument");
+  std::string dir(directory), text;
+  if (!read_file(dir + objname, &text)) return fail(MCPT_ERR_IO, "load_mtl_bump_maps: cannot read " + dir + objname);
+  std::vector<BumpMap> maps;
+  const char *p = text.data(), *end = p + text.size();
+  while (p < end) {  // mcpt_load_obj's mtllib rule: of each line, the first library that loads
+    const char *eol = (const char *)std::memchr(p, '\n', end - p);
+    if (!eol) eol = end;
+    const char *q = p;
+    while (q < eol && (*q == ' ' || *q == '\t')) ++q;
+    if (eol - q >= 7 && std::strncmp(q, "mtllib", 6) == 0 && (q[6] == ' ' || q[6] == '\t')) {
+      q += 7;
+      for (;;) {
+        Tok t = next_token(q, eol);
+        if (t.p == t.e) break;
+        std::string mt;
+        if (read_file(dir + std::string(t.p, t.e), &mt)) {
+          parse_mtl_bump_maps(mt.data(), mt.data() + mt.size(), &maps);
+          break;
+        }
+      }
+    }
+    p = eol + 1;
+  }
+  return emit_bump_maps(maps, names, kinds, bm, n_bytes, n_materials);
 }

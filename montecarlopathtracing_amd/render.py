@@ -630,6 +630,62 @@ class Renderer:
         torch.cuda.current_stream().synchronize()  # (the inputs above are temporaries)
         return out
 
+    # ------------------------------------------ bump and normal maps (opt-in)
+    def set_normal_maps(self, scene, uv, tri_map, images):
+        """mcpt_scene_set_normal_maps: every hit on `scene` is shaded with its
+        normal perturbed by the bilinear, repeating lookup of the triangle's
+        tangent-space normal map.  uv: (n_tris, 3, 2) float32 in the upload's
+        triangle order; tri_map: n_tris int32 indices into `images`, -1:
+        unmapped; images: (h, w, 3) float32 unit normals with z > 0, row 0 the
+        top (scene.load_bump_maps returns the three).  Replaces previous ones
+        and drops the primary-hit cache."""
+        u = np.ascontiguousarray(uv, np.float32)
+        t = np.ascontiguousarray(tri_map, np.int32)
+        n = len(scene.data.tris) if hasattr(scene.data, "tris") else scene.data[0].numel() // L.TRIANGLE.itemsize
+        if u.size != n * 6 or t.size != n:
+            raise ValueError("set_normal_maps: %d triangles need (n, 3, 2) uvs and n indices, got %r and %r" %
+                             (n, u.shape, t.shape))
+        imgs = [np.ascontiguousarray(im, np.float32) for im in images]
+        for k, im in enumerate(imgs):
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise ValueError("set_normal_maps: image %d must be (height, width, 3), got %r" % (k, im.shape))
+        recs = (L.NormalMapImage * max(len(imgs), 1))()
+        for k, im in enumerate(imgs):
+            recs[k].xyz, recs[k].width, recs[k].height = L.ptr(im), im.shape[1], im.shape[0]
+        nm = L.NormalMaps(L.ptr(u), L.ptr(t), len(imgs), ctypes.cast(recs, ctypes.c_void_p))
+        L.check(L.lib().mcpt_scene_set_normal_maps(self.ctx, scene.handle, ctypes.byref(nm)))
+
+    def clear_normal_maps(self, scene):
+        """Back to the unmapped normals (the bits of a scene that never had maps)."""
+        L.check(L.lib().mcpt_scene_set_normal_maps(self.ctx, scene.handle, None))
+
+    def bump_eval(self, scene, tri_ids, points, dirs, normals):
+        """mcpt_bump_eval: the mapped shading normal at (triangle, hit point,
+        ray direction, unmapped normal N) queries on a mapped scene: a float32
+        (n, 4) device tensor (zeros for an index outside the scene).  tri_ids:
+        n int32; points, dirs, normals: (n, 3) or (n, 4), host arrays or device
+        (n, 4) float32 tensors."""
+        if torch.is_tensor(tri_ids):
+            ids = tri_ids.to(self.device, torch.int32).contiguous()
+        else:
+            ids = torch.as_tensor(np.ascontiguousarray(tri_ids, np.int32)).to(self.device)
+        n = ids.numel()
+
+        def dev4(x):
+            if torch.is_tensor(x):
+                return x.to(self.device, torch.float32).reshape(n, 4).contiguous()
+            a = np.asarray(x, np.float32).reshape(n, -1)
+            q = np.zeros((n, 4), np.float32)
+            q[:, :a.shape[1]] = a
+            return torch.from_numpy(q).to(self.device)
+
+        p, d, nn = dev4(points), dev4(dirs), dev4(normals)
+        out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        L.check(L.lib().mcpt_bump_eval(self.ctx, scene.handle, L.ptr(ids), L.ptr(p), L.ptr(d), L.ptr(nn), n,
+                                       L.ptr(out), _stream()))
+        torch.cuda.current_stream().synchronize()  # (the inputs above are temporaries)
+        return out
+
     def first_hit_albedo(self, scene, hits):
         """Renderer.denoise's `albedo` for a textured scene: texture_eval at
         the first hits (first_hits' records), forced to 1 where the first hit

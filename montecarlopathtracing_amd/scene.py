@@ -406,6 +406,150 @@ def load_textures(directory, objname, mats, mat_index):
     return uv, tri_tex, images
 
 
+# ------------------------------------------- bump and normal maps (opt-in)
+BUMP_NONE, BUMP_HEIGHT, BUMP_NORMAL = 0, 1, 2  # mcpt_load_mtl_bump_maps' kinds
+
+
+def height_to_normal(hmap, k=1.0):
+    """A height map (h, w) -> (h, w, 3) float32 tangent-space unit normals, row
+    0 the top, +v up.  Central differences with wrap, per texel: gx = (h[i+1] -
+    h[i-1]) / 2, gy = (h[row j-1] - h[row j+1]) / 2, m = normalize(-k gx, -k
+    gy, 1) in float64, rounded once.  k = bm * scale: MTL carries no world
+    scale, so slopes are per texel and the user's scale stands in for it."""
+    h = np.asarray(hmap, np.float64)
+    if h.ndim != 2 or h.size == 0:
+        raise ValueError("height_to_normal: a (height, width) map, got %r" % (h.shape,))
+    k = float(k)
+    if not np.isfinite(k):
+        raise ValueError("height_to_normal: k must be finite, got %r" % (k,))
+    gx = (np.roll(h, -1, axis=1) - np.roll(h, 1, axis=1)) / 2.0
+    gy = (np.roll(h, 1, axis=0) - np.roll(h, -1, axis=0)) / 2.0
+    m = np.stack([-k * gx, -k * gy, np.ones_like(h)], axis=2)
+    m /= np.sqrt((m * m).sum(axis=2, keepdims=True))
+    return _clean_normals(m)
+
+
+def _clean_normals(m):
+    """float64 (h, w, 3) vectors -> float32 unit normals; a texel with z <= 0,
+    zero length or a non-finite component becomes (0, 0, 1)."""
+    m = np.array(m, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        l = np.sqrt((m * m).sum(axis=2))
+        bad = ~np.isfinite(m).all(axis=2) | ~(l > 0) | ~np.isfinite(l) | ~(m[..., 2] > 0)
+        m = m / np.where(bad, 1.0, l)[..., None]
+    out = m.astype(np.float32) + np.float32(0.0)  # (-0 -> +0)
+    bad |= ~(out[..., 2] > 0)
+    out[bad] = (0.0, 0.0, 1.0)
+    return np.ascontiguousarray(out)
+
+
+def decode_normal_image(img):
+    """A normal-map image -> (h, w, 3) float32 unit normals.  uint8: 2 c / 255 -
+    1 per channel, raw (no sRGB decode), then normalised; float data is taken
+    as it is and normalised.  A texel with z <= 0 or zero length becomes
+    (0, 0, 1)."""
+    a = np.asarray(img)
+    if a.ndim != 3 or a.shape[2] < 3:
+        raise ValueError("decode_normal_image: (height, width, 3), got %r" % (a.shape,))
+    if a.dtype == np.uint8:
+        return _clean_normals(2.0 * a[..., :3].astype(np.float64) / 255.0 - 1.0)
+    return _clean_normals(a[..., :3].astype(np.float64))
+
+
+def _read_raw_image(path):
+    """An image's raw channels: (h, w, 3) uint8 for 8-bit files, float32 for
+    .hdr.  A missing or unreadable file raises ValueError naming it."""
+    import os
+    if not os.path.isfile(path):
+        raise ValueError("map file %s does not exist" % path)
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".png":
+        return read_png(path)
+    if ext == ".hdr":
+        try:
+            return np.ascontiguousarray(read_hdr(path), np.float32)
+        except L.MCPTError as e:
+            raise ValueError("%s: %s" % (path, e))
+    try:
+        from PIL import Image
+    except ImportError:
+        raise ValueError("%s: only .png (8-bit, non-interlaced) and .hdr maps are read without Pillow" % path)
+    try:
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB"), np.uint8)
+    except Exception as e:  # Pillow raises its own types for unknown or damaged files
+        raise ValueError("%s: %s" % (path, e))
+
+
+def read_bump_map(path, kind, k=1.0):
+    """A map file as (h, w, 3) float32 unit normals.  BUMP_NORMAL:
+    decode_normal_image of the raw channels; BUMP_HEIGHT: height_to_normal of
+    their mean (8-bit: / 255, no sRGB decode) with slope factor k."""
+    raw = _read_raw_image(path)
+    if kind == BUMP_NORMAL:
+        return decode_normal_image(raw)
+    h = raw[..., :3].astype(np.float64).mean(axis=2)
+    if raw.dtype == np.uint8:
+        h = h / 255.0
+    return height_to_normal(np.nan_to_num(h, nan=0.0, posinf=3.0e38, neginf=-3.0e38), k)
+
+
+def _bump_maps(call, *head):
+    nb, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(call(*head, None, None, None, ctypes.byref(nb), ctypes.byref(nm)))
+    buf = np.zeros(max(nb.value, 1), np.uint8)
+    kinds = np.zeros(max(nm.value, 1), np.int32)
+    bm = np.ones(max(nm.value, 1), np.float32)
+    L.check(call(*head, L.ptr(buf), L.ptr(kinds), L.ptr(bm), ctypes.byref(nb), ctypes.byref(nm)))
+    n = nm.value
+    return list(zip(_names(buf[:nb.value], n), [int(x) for x in kinds[:n]], [float(x) for x in bm[:n]]))
+
+
+def load_mtl_bump_maps(directory, objname):
+    """Each material's (file name, kind, -bm value) in load_object's material
+    order: kind BUMP_NORMAL for `norm`, BUMP_HEIGHT for `map_Bump`, `map_bump`
+    or `bump`, BUMP_NONE with "" (mcpt_load_mtl_bump_maps)."""
+    return _bump_maps(L.lib().mcpt_load_mtl_bump_maps, directory.encode(), objname.encode())
+
+
+def mtl_bump_maps_from_text(text):
+    """load_mtl_bump_maps on MTL text (bytes or str) in memory."""
+    t = text.encode() if isinstance(text, str) else bytes(text)
+    src = np.frombuffer(t, np.uint8) if t else np.zeros(0, np.uint8)
+    return _bump_maps(L.lib().mcpt_mtl_bump_maps_from_text, L.ptr(src) if len(src) else None, len(src))
+
+
+def load_bump_maps(directory, objname, mats, mat_index, scale=1.0):
+    """What Renderer.set_normal_maps takes for an OBJ model: (uv[n, 3, 2]
+    float32, tri_map[n] int32, images: list of (h, w, 3) float32 unit normals).
+    tri_map[i] = -1 where triangle i has no `vt` or its material no map.  A
+    height map's slopes are per texel times bm * scale.  A named file that is
+    missing raises ValueError naming it; a model with maps but no `vt` at all
+    comes back unmapped after one warning line."""
+    import os
+    import sys
+    uv, has = load_obj_uvs(directory, objname)
+    idx = np.asarray(mat_index, np.int32)
+    if len(idx) != len(uv):
+        raise ValueError("load_bump_maps: %d material indices for %d triangles" % (len(idx), len(uv)))
+    maps = load_mtl_bump_maps(directory, objname)
+    maps = (maps + [("", BUMP_NONE, 1.0)] * len(mats))[:max(len(mats), len(maps))]
+    tri_map = np.full(len(uv), -1, np.int32)
+    images, slot = [], {}
+    used = sorted(set(int(m) for m in idx[has] if 0 <= m < len(maps) and maps[m][0]))
+    for m in used:
+        name, kind, bm = maps[m]
+        key = (os.path.join(directory, name), kind, bm if kind == BUMP_HEIGHT else 1.0)
+        if key not in slot:
+            slot[key] = len(images)
+            images.append(read_bump_map(key[0], kind, bm * float(scale)))
+        tri_map[has & (idx == m)] = slot[key]
+    if any(m[0] for m in maps) and not has.any():
+        print("warning: %s names bump or normal maps but has no texture coordinates (vt): rendering unmapped" % objname,
+              file=sys.stderr)
+    return uv, tri_map, images
+
+
 class SceneData:
     """Host-side scene: packed triangles, HLBVH nodes, materials."""
 

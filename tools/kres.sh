@@ -3,6 +3,7 @@
 #   bash tools/kres.sh [extra hipcc flags]
 #   bash tools/kres.sh -DMCPT_SMOOTH_TU     the smooth-shading (N) forms' translation unit instead
 #   bash tools/kres.sh -DMCPT_TEXTURE_TU    the textured forms' translation unit instead
+#   bash tools/kres.sh -DMCPT_BUMP_TU       the mapped (normal-map) forms' translation unit instead
 cd "$(dirname "$0")/../montecarlopathtracing_amd/csrc"
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=on \
   -fno-hip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function "$@" -c mcpt_device.hip -o /tmp/kres.$$.o \
