@@ -365,6 +365,13 @@ int mcpt_scene_destroy(mcpt_scene *scene);
 int mcpt_scene_upload_device(mcpt_ctx *ctx, const mcpt_triangle *tris_dev, int64_t n_tris,
                              const mcpt_bvh_node *nodes_dev, int64_t n_nodes, const mcpt_material *mats,
                              int32_t n_mats, void *stream, mcpt_scene **out);
+/* Process-wide upload option, on by default: the search tree of the scenes
+ * uploaded from here on (either path, up to 131072 triangles) is optimised by
+ * `passes` rounds of subtree reinsertion and a collapse that keeps the plain
+ * tree's stack need.  0 = the plain tree.  The tree only
+ * sets the search's cost, never a result.  passes in [0, 16]; default 3.    */
+int mcpt_set_sah_optimize(int32_t passes);
+int mcpt_get_sah_optimize(int32_t *passes);
 /* A scene's device arrays copied to the host (introspection).  which: 0 the
  * search tree (128-B nodes), 1 its quantized nodes, 2 the reference tree
  * 4-wide, 3 the binary child-box nodes, 4 triangles, 5 quantized-path

@@ -151,6 +151,8 @@ SIGNATURES = {
     "mcpt_scene_destroy": (_I32, [_P]),
     "mcpt_scene_upload_device": (_I32, [_P, _P, _I64, _P, _I64, _P, _I32, _P, _P]),
     "mcpt_scene_read": (_I32, [_P, _I32, _P, _I64, _P]),
+    "mcpt_set_sah_optimize": (_I32, [_I32]),
+    "mcpt_get_sah_optimize": (_I32, [_P]),
     "mcpt_render_frames": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "mcpt_render_frames_lens": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcpt_generate_rays_lens": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),

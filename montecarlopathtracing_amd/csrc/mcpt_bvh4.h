@@ -30,7 +30,29 @@ struct LeafRef {
 // bounds the stack entries any visiting order can hold (k-1 per k-slot node
 // on a root-to-leaf path).  Deterministic for a given input; threads only
 // split the work.  Returns 0, or -1 for an empty input.
-int build_sah4(const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out, int32_t *stack_need, int threads);
+//
+// opt (optional) turns on the tree optimisation: `passes`
+// rounds of subtree reinsertion on the binary tree, then the least-cost
+// collapse whose stack need stays within a cap.  The cap is the need of the
+// plain tree (no pass, uncapped collapse) unless need_cap > 0 forces another.
+// Where the cap is infeasible or the optimised tree costs more than the plain
+// one, the plain tree comes out.  Without opt, or with passes <= 0, the plain
+// tree comes out, byte for byte.  The optimisation is sequential: the result
+// does not depend on `threads` either.
+struct SahOptimize {
+  int passes = 3;
+  int need_cap = 0;
+  // results
+  bool optimized = false;    // the optimised tree was emitted
+  double cost_plain = 0.0;   // collapse cost of the plain tree
+  double cost_out = 0.0;     // collapse cost of the emitted tree
+  int32_t need_plain = 0;    // stack need of the plain tree
+  int64_t moved = 0;         // subtrees moved, all passes
+  int64_t extra_bytes = 0;   // peak memory the optimisation added to the plain build
+};
+constexpr int64_t kSahOptimizeMaxLeaves = 131072;  // both upload paths optimise at or below this many leaves
+int build_sah4(const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out, int32_t *stack_need, int threads,
+               SahOptimize *opt = nullptr);
 
 // 64-B quantized form of a Node4Rec, the search-tree node k_render reads with
 // four 16-B gathers instead of seven.  Per axis a float origin o_a and a

@@ -2943,6 +2943,20 @@ static int node96_device(mcpt_scene *s, int64_t n_near4, int64_t n_nodes4, int64
   return done(MCPT_OK);
 }
 
+// Process-wide upload option: the passes of the search tree's optimisation
+// (mcpt_sah.cpp; 0 = the plain tree).  It only sets the search's cost.
+static std::atomic<int32_t> g_sah_passes{3};
+int mcpt_set_sah_optimize(int32_t passes) {
+  if (passes < 0 || passes > 16) return mcpt::fail(MCPT_ERR_ARG, "set_sah_optimize: passes outside [0, 16]");
+  g_sah_passes = passes;
+  return MCPT_OK;
+}
+int mcpt_get_sah_optimize(int32_t *out) {
+  if (!out) return mcpt::fail(MCPT_ERR_ARG, "get_sah_optimize: bad argument");
+  *out = g_sah_passes;
+  return MCPT_OK;
+}
+
 int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, const mcpt_bvh_node *nodes,
                       int64_t n_nodes, const mcpt_material *mats, int32_t n_mats, mcpt_scene **out) {
   if (!ctx || !tris || !nodes || !mats || !out || n_tris <= 0 || n_mats <= 0)
@@ -2959,7 +2973,9 @@ int mcpt_scene_upload(mcpt_ctx *ctx, const mcpt_triangle *tris, int64_t n_tris, 
   std::vector<mcpt::Node4Rec> near;
   if (n_int > 0) {
     const unsigned hw = std::thread::hardware_concurrency();
-    if (mcpt::build_sah4(leaf_list(nodes, n_nodes, n), near, &depth_near, (int)std::min(16u, std::max(1u, hw))) != 0)
+    mcpt::SahOptimize opt;  // the optimised tree at or below the leaf limit, as mcpt_scene_upload_device
+    opt.passes = n <= mcpt::kSahOptimizeMaxLeaves ? (int)g_sah_passes : 0;
+    if (mcpt::build_sah4(leaf_list(nodes, n_nodes, n), near, &depth_near, (int)std::min(16u, std::max(1u, hw)), &opt) != 0)
       return mcpt::fail(MCPT_ERR_ARG, "scene_upload: no leaves");
   } else {
     near.resize(1);
@@ -3011,7 +3027,7 @@ int mcpt_scene_upload_device(mcpt_ctx *ctx, const mcpt_triangle *tris_dev, int64
   if (n_nodes != 2 * n_tris - 1) return mcpt::fail(MCPT_ERR_ARG, "scene_upload_device: expected 2n-1 BVH nodes");
   HIP_OK(hipSetDevice(ctx->device));
   mcpt::DeviceScene D;
-  int rc = mcpt::build_scene_device(tris_dev, n_tris, nodes_dev, n_mats, (hipStream_t)stream, &D);
+  int rc = mcpt::build_scene_device(tris_dev, n_tris, nodes_dev, n_mats, (int)g_sah_passes, (hipStream_t)stream, &D);
   mcpt_scene *s = new mcpt_scene();  // owns D's arrays from here, on failure too
   s->device = ctx->device;
   s->near4 = (DevNode4 *)D.near4, s->near4q = (DevNode4Q *)D.near4q;

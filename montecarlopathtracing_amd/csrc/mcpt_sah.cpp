@@ -6,14 +6,18 @@
 // the reference tree when it could).  Only the search cost depends on this
 // tree, so it is built for that: surface-area-heuristic splits over 32
 // centroid bins per axis, collapsed to 4-wide nodes by an SAH-optimal
-// dynamic programme, one reference leaf per slot.
+// dynamic programme, one reference leaf per slot.  On request (SahOptimize)
+// the binary tree is first improved by subtree reinsertion, and the collapse
+// then keeps the stack need of the plain tree ("optimisation" below).
 #include <algorithm>
 #include <array>
 #include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <thread>
+#include <utility>
 
 #include "mcpt_bvh4.h"
 
@@ -139,26 +143,52 @@ struct Builder {
   }
 };
 
-}  // namespace
+constexpr double kInf = std::numeric_limits<double>::infinity();
 
-int build_sah4(const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out, int32_t *stack_need, int threads) {
-  const int64_t m = (int64_t)leaves.size();
-  out.clear();
-  *stack_need = 1;
-  if (m <= 0) return -1;
-  Builder B(leaves);
-  B.max_threads = std::max(1, threads);
-  B.cen.resize(3 * (size_t)m);
-  B.idx.resize((size_t)m);
-  for (int64_t i = 0; i < m; ++i) {
-    for (int a = 0; a < 3; ++a) B.cen[3 * i + a] = 0.5f * (leaves[i].box[2 * a] + leaves[i].box[2 * a + 1]);
-    B.idx[i] = (int32_t)i;
+// one wide node from its entries (binary subtree roots, left to right); the
+// internal entries get the next free ids, returned in child_out
+void emit_node(const std::vector<BinNode> &N, const std::vector<LeafRef> &leaves, const int32_t *kids, int nk,
+               int32_t self, std::vector<Node4Rec> &out, int32_t *child_out) {
+  Node4Rec rec;
+  std::memset(&rec, 0, sizeof(rec));
+  for (int k = 0; k < 4; ++k) {
+    child_out[k] = -1;
+    if (k >= nk) {
+      rec.link[k] = kEmptySlot4;
+      continue;
+    }
+    const BinNode &c = N[kids[k]];
+    std::memcpy(rec.q + 6 * k, c.box, sizeof(c.box));
+    if (c.item >= 0) {
+      rec.link[k] = ~leaves[c.item].tri;
+    } else {
+      child_out[k] = (int32_t)out.size();
+      rec.link[k] = child_out[k];
+      out.emplace_back();
+    }
   }
-  B.nodes.resize(2 * (size_t)m - 1);
-  B.build(0, m, 0, 0);
-  if (m == 1) return 0;  // a single leaf: the kernels handle it without a node
+  out[self] = rec;
+}
 
-  const std::vector<BinNode> &N = B.nodes;
+// the stack entries any visiting order of the wide tree can hold
+int32_t wide_need(const std::vector<Node4Rec> &out) {
+  // children are allocated when their parent is emitted: ids only grow down the tree
+  std::vector<int32_t> need(out.size(), 0);
+  for (int64_t k = (int64_t)out.size() - 1; k >= 0; --k) {
+    int ns = 0, below = 0;
+    for (int s = 0; s < 4; ++s) {
+      if (out[k].link[s] == kEmptySlot4) continue;
+      ++ns;
+      if (out[k].link[s] >= 0) below = std::max(below, need[out[k].link[s]]);
+    }
+    need[k] = ns - 1 + below;
+  }
+  return need[0];
+}
+
+// The plain collapse of the binary tree N (children after parents, root 0)
+// into `out`; returns its cost.
+double collapse_plain(const std::vector<BinNode> &N, const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out) {
   // collapse to 4-wide nodes, SAH-optimally (dynamic programme over the binary
   // tree): f[x][k] = the least cost of x's subtree as at most k slot entries,
   // where a wide node costs area x C_STEP plus its entries and a leaf entry
@@ -213,40 +243,307 @@ int build_sah4(const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out, i
     int nk = 0;
     entries(N[p.bin].left, wide[p.bin][0], kids, nk);
     entries(N[p.bin].right, wide[p.bin][1], kids, nk);
-    Node4Rec rec;
-    std::memset(&rec, 0, sizeof(rec));
-    int32_t child_out[4] = {-1, -1, -1, -1};
-    for (int k = 0; k < 4; ++k) {
-      if (k >= nk) {
-        rec.link[k] = kEmptySlot4;
-        continue;
-      }
-      const BinNode &c = N[kids[k]];
-      std::memcpy(rec.q + 6 * k, c.box, sizeof(c.box));
-      if (c.item >= 0) {
-        rec.link[k] = ~leaves[c.item].tri;
-      } else {
-        child_out[k] = (int32_t)out.size();
-        rec.link[k] = child_out[k];
-        out.emplace_back();
-      }
-    }
-    out[p.out] = rec;
+    int32_t child_out[4];
+    emit_node(N, leaves, kids, nk, p.out, out, child_out);
     for (int k = nk - 1; k >= 0; --k)  // preorder: slot 0's subtree next
       if (child_out[k] >= 0) todo.push_back(Pending{kids[k], child_out[k]});
   }
-  // children are allocated when their parent is emitted: ids only grow down the tree
-  std::vector<int32_t> need(out.size(), 0);
-  for (int64_t k = (int64_t)out.size() - 1; k >= 0; --k) {
-    int ns = 0, below = 0;
-    for (int s = 0; s < 4; ++s) {
-      if (out[k].link[s] == kEmptySlot4) continue;
-      ++ns;
-      if (out[k].link[s] >= 0) below = std::max(below, need[out[k].link[s]]);
-    }
-    need[k] = ns - 1 + below;
+  return f[0][1];
+}
+
+// ------------------------------------------------------------ optimisation
+// Subtree reinsertion (Bittner, Hapala, Havran: "Fast insertion-based
+// optimization of bounding volume hierarchies", 2013) on the binary tree.  A
+// node and its parent are taken out, the sibling moving up, and put back where
+// the summed area of the internal nodes grows least; the old place is one of
+// the candidates, so the sum never rises.  Every internal box stays
+// grow(left box, right box) bit for bit, as Builder::build makes it.
+struct Reinserter {
+  std::vector<BinNode> &N;
+  std::vector<int32_t> par;
+  std::vector<std::pair<double, int32_t>> heap;  // (induced area above, node), least first
+
+  explicit Reinserter(std::vector<BinNode> &n) : N(n), par(n.size(), -1) {
+    for (size_t x = 0; x < N.size(); ++x)
+      if (N[x].item < 0) par[N[x].left] = par[N[x].right] = (int32_t)x;
   }
-  *stack_need = std::max(need[0], 1);
+  static void unite(float *o, const float *l, const float *r) {
+    std::memcpy(o, l, 6 * sizeof(float));
+    Builder::grow(o, r);
+  }
+  static double united_area(const float *a, const float *b) {
+    float u[6];
+    unite(u, a, b);
+    return Builder::area(u);
+  }
+  // x and its ancestors, until a box stays what it was
+  void refit(int32_t x) {
+    for (; x >= 0; x = par[x]) {
+      float b[6];
+      unite(b, N[N[x].left].box, N[N[x].right].box);
+      if (!std::memcmp(b, N[x].box, sizeof(b))) break;
+      std::memcpy(N[x].box, b, sizeof(b));
+    }
+  }
+  // p, with children (l, r), takes y's place
+  void attach(int32_t p, int32_t y, int32_t l, int32_t r) {
+    const int32_t q = par[y];
+    (N[q].left == y ? N[q].left : N[q].right) = p;
+    par[p] = q;
+    N[p].left = l, N[p].right = r;
+    par[l] = par[r] = p;
+    unite(N[p].box, N[l].box, N[r].box);
+    refit(q);
+  }
+  // returns whether x moved
+  bool reinsert(int32_t x) {
+    const int32_t p = par[x];
+    if (p <= 0) return false;  // the root, or a child of the root
+    const int32_t gp = par[p];
+    const bool was_left = N[p].left == x;
+    const int32_t s = was_left ? N[p].right : N[p].left;
+    (N[gp].left == p ? N[gp].left : N[gp].right) = s;
+    par[s] = gp;
+    refit(gp);
+    const float *bx = N[x].box;
+    const double ax = Builder::area(bx);
+    // the old place, costed as the search below costs it: down from the root
+    int32_t path[256];
+    int np = 0;
+    bool deep = false;
+    for (int32_t a = gp; a >= 0; a = par[a]) {
+      if (np == 256) {
+        deep = true;
+        break;
+      }
+      path[np++] = a;
+    }
+    double best = kInf;
+    int32_t best_y = s;
+    if (!deep) {
+      double ind = 0.0;
+      for (int k = np - 1; k >= 0; --k) ind = ind + (united_area(N[path[k]].box, bx) - Builder::area(N[path[k]].box));
+      best = ind + united_area(N[s].box, bx);
+    }
+    // branch and bound from the root's children (the root keeps its id)
+    heap.clear();
+    auto cmp = [](const std::pair<double, int32_t> &a, const std::pair<double, int32_t> &b) { return a > b; };
+    const double ind0 = 0.0 + (united_area(N[0].box, bx) - Builder::area(N[0].box));
+    heap.emplace_back(ind0, N[0].left), std::push_heap(heap.begin(), heap.end(), cmp);
+    heap.emplace_back(ind0, N[0].right), std::push_heap(heap.begin(), heap.end(), cmp);
+    while (!heap.empty()) {
+      std::pop_heap(heap.begin(), heap.end(), cmp);
+      const std::pair<double, int32_t> e = heap.back();
+      heap.pop_back();
+      if (!(e.first + ax < best)) break;  // nothing left can do better
+      const int32_t y = e.second;
+      const double direct = united_area(N[y].box, bx);
+      if (e.first + direct < best) best = e.first + direct, best_y = y;
+      if (N[y].item >= 0) continue;
+      const double below = e.first + (direct - Builder::area(N[y].box));
+      if (below + ax < best) {
+        heap.emplace_back(below, N[y].left), std::push_heap(heap.begin(), heap.end(), cmp);
+        heap.emplace_back(below, N[y].right), std::push_heap(heap.begin(), heap.end(), cmp);
+      }
+    }
+    if (best_y == s) {
+      attach(p, s, was_left ? x : s, was_left ? s : x);
+      return false;
+    }
+    attach(p, best_y, best_y, x);
+    return true;
+  }
+  // one pass over every node below the root's children, largest area first
+  int64_t pass() {
+    std::vector<std::pair<double, int32_t>> order;
+    for (size_t x = 1; x < N.size(); ++x)
+      if (par[x] > 0) order.emplace_back(-Builder::area(N[x].box), (int32_t)x);
+    std::sort(order.begin(), order.end());
+    int64_t moved = 0;
+    for (const auto &o : order) moved += reinsert(o.second) ? 1 : 0;
+    return moved;
+  }
+  // the tree in depth-first preorder (children after parents, root 0)
+  std::vector<BinNode> preorder() const {
+    std::vector<BinNode> out;
+    out.reserve(N.size());
+    std::vector<std::pair<int32_t, int32_t>> todo(1, {0, -1});  // (node, new id of its parent)
+    while (!todo.empty()) {
+      const std::pair<int32_t, int32_t> t = todo.back();
+      todo.pop_back();
+      const int32_t id = (int32_t)out.size();
+      out.push_back(N[t.first]);
+      if (t.second >= 0) (out[t.second].left < 0 ? out[t.second].left : out[t.second].right) = id;
+      if (N[t.first].item >= 0) continue;
+      out[id].left = out[id].right = -1;  // filled in as the children come out, the left one first
+      todo.push_back({N[t.first].right, id});
+      todo.push_back({N[t.first].left, id});
+    }
+    return out;
+  }
+};
+
+// The least-cost collapse of N whose stack need stays within `cap`: the plain
+// collapse's programme with a budget axis.  g = f[.][1]: x as a wide node of
+// need <= b; a wide node of s slots leaves its entries the budget b - (s - 1).
+// A node's rows stop changing once b reaches what its subtree can use, so each
+// node keeps rows 0 .. that budget only (leaves keep none).  Returns the cost,
+// kInf where no collapse fits the cap; *bytes = the table's size.
+struct CappedCollapse {
+  struct Row {
+    double f[4];    // at most 1..4 entries
+    int8_t cut[4];  // as collapse_plain's
+    int8_t wa, wc;  // x as a wide node: entries from the left / right child
+  };
+  const std::vector<BinNode> &N;
+  std::vector<Row> rows;
+  std::vector<uint32_t> first;
+  std::vector<uint8_t> count;  // rows of x (cap + 1 <= 255)
+  static constexpr double C_STEP = 1.0, C_TRI = MCPT_COLLAPSE_CTRI;
+
+  explicit CappedCollapse(const std::vector<BinNode> &n) : N(n), first(n.size(), 0), count(n.size(), 0) {}
+
+  const Row *row(int32_t x, int b) const { return &rows[first[x] + (size_t)std::min<int>(b, count[x] - 1)]; }
+  double f(int32_t x, int k, int b) const {
+    if (b < 0) return kInf;
+    if (N[x].item >= 0) return Builder::area(N[x].box) * C_TRI;
+    return row(x, b)->f[k - 1];
+  }
+  int cut(int32_t x, int k, int b) const { return N[x].item >= 0 ? 0 : row(x, b)->cut[k - 1]; }
+
+  double run(int cap) {
+    cap = std::min(cap, 254);
+    std::vector<Row> tmp;
+    for (int64_t x = (int64_t)N.size() - 1; x >= 0; --x) {  // children have larger ids than their parent
+      if (N[x].item >= 0) continue;
+      const int32_t l = N[x].left, r = N[x].right;
+      const double sa = Builder::area(N[x].box);
+      // the children's rows end at count - 1 (a leaf: one constant row); three more budget opens every split
+      const int top = std::min(cap, std::max<int>({1, count[l], count[r]}) - 1 + 3);
+      tmp.assign((size_t)top + 1, Row());
+      for (int b = 0; b <= top; ++b) {
+        Row &R = tmp[b];
+        double bw = kInf;
+        R.wa = R.wc = 0;
+        for (int a = 1; a <= 3; ++a)
+          for (int c = 1; a + c <= 4; ++c) {
+            const double v = f(l, a, b - (a + c - 1)) + f(r, c, b - (a + c - 1));
+            if (v < bw) bw = v, R.wa = (int8_t)a, R.wc = (int8_t)c;
+          }
+        R.f[0] = bw < kInf ? sa * C_STEP + bw : kInf;
+        R.cut[0] = 0;
+        for (int k = 2; k <= 4; ++k) {
+          R.f[k - 1] = R.f[k - 2];
+          R.cut[k - 1] = R.cut[k - 2];
+          for (int a = 1; a < k; ++a) {
+            const double v = f(l, a, b) + f(r, k - a, b);
+            if (v < R.f[k - 1]) R.f[k - 1] = v, R.cut[k - 1] = (int8_t)a;
+          }
+        }
+      }
+      int keep = top + 1;  // costs only fall with b: rows equal to the last one add nothing
+      while (keep > 1 && !std::memcmp(tmp[keep - 2].f, tmp[top].f, sizeof(tmp[top].f))) --keep;
+      first[x] = (uint32_t)rows.size();
+      count[x] = (uint8_t)keep;
+      rows.insert(rows.end(), tmp.begin(), tmp.begin() + keep);
+    }
+    return f(0, 1, cap);
+  }
+  int64_t bytes() const {
+    return (int64_t)(rows.capacity() * sizeof(Row) + first.capacity() * sizeof(uint32_t) + count.capacity());
+  }
+
+  void entries(int32_t x, int k, int b, int32_t *e, int &ne) const {
+    const int a = cut(x, k, b);
+    if (a == 0) {
+      e[ne++] = x;
+      return;
+    }
+    entries(N[x].left, a, b, e, ne);
+    entries(N[x].right, k - a, b, e, ne);
+  }
+  // after run(cap) gave a finite cost
+  void emit(int cap, const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out) const {
+    struct Pending {
+      int32_t bin, out, budget;
+    };
+    std::vector<Pending> todo(1, Pending{0, 0, std::min(cap, 254)});
+    out.emplace_back();
+    while (!todo.empty()) {
+      const Pending p = todo.back();
+      todo.pop_back();
+      const Row *R = row(p.bin, p.budget);
+      const int below = p.budget - (R->wa + R->wc - 1);
+      int32_t kids[4] = {-1, -1, -1, -1}, child_out[4];
+      int nk = 0;
+      entries(N[p.bin].left, R->wa, below, kids, nk);
+      entries(N[p.bin].right, R->wc, below, kids, nk);
+      emit_node(N, leaves, kids, nk, p.out, out, child_out);
+      for (int k = nk - 1; k >= 0; --k)  // preorder: slot 0's subtree next
+        if (child_out[k] >= 0) todo.push_back(Pending{kids[k], child_out[k], below});
+    }
+  }
+};
+
+}  // namespace
+
+int build_sah4(const std::vector<LeafRef> &leaves, std::vector<Node4Rec> &out, int32_t *stack_need, int threads,
+               SahOptimize *opt) {
+  const int64_t m = (int64_t)leaves.size();
+  out.clear();
+  *stack_need = 1;
+  if (opt) {
+    opt->optimized = false;
+    opt->cost_plain = opt->cost_out = 0.0;
+    opt->need_plain = 1;
+    opt->moved = opt->extra_bytes = 0;
+  }
+  if (m <= 0) return -1;
+  Builder B(leaves);
+  B.max_threads = std::max(1, threads);
+  B.cen.resize(3 * (size_t)m);
+  B.idx.resize((size_t)m);
+  for (int64_t i = 0; i < m; ++i) {
+    for (int a = 0; a < 3; ++a) B.cen[3 * i + a] = 0.5f * (leaves[i].box[2 * a] + leaves[i].box[2 * a + 1]);
+    B.idx[i] = (int32_t)i;
+  }
+  B.nodes.resize(2 * (size_t)m - 1);
+  B.build(0, m, 0, 0);
+  if (m == 1) return 0;  // a single leaf: the kernels handle it without a node
+
+  const double cost_plain = collapse_plain(B.nodes, leaves, out);
+  const int32_t need_plain = wide_need(out);
+  *stack_need = std::max(need_plain, 1);
+  if (!opt) return 0;
+  opt->cost_plain = opt->cost_out = cost_plain;
+  opt->need_plain = *stack_need;
+  if (opt->passes <= 0 || m < 3) return 0;
+
+  std::vector<BinNode> T;
+  {
+    Reinserter R(B.nodes);  // B.nodes is spent: the plain tree is in `out`
+    for (int k = 0; k < opt->passes; ++k) {
+      const int64_t moved = R.pass();
+      opt->moved += moved;
+      if (!moved) break;
+    }
+    opt->extra_bytes = (int64_t)(R.par.capacity() * sizeof(int32_t) + (B.nodes.size() - 1) * sizeof(std::pair<double, int32_t>));
+    T = R.preorder();
+  }
+  const int cap = opt->need_cap > 0 ? opt->need_cap : need_plain;
+  CappedCollapse C(T);
+  const double cost = C.run(cap);
+  opt->extra_bytes = std::max(opt->extra_bytes, (int64_t)(T.capacity() * sizeof(BinNode)) + C.bytes());
+  if (!(cost <= cost_plain)) return 0;  // no collapse within the cap, or a dearer one: the plain tree stays
+  std::vector<Node4Rec> better;
+  C.emit(cap, leaves, better);
+  const int32_t need = wide_need(better);
+  if (need > std::max(cap, 1)) return 0;
+  opt->extra_bytes += (int64_t)(better.capacity() * sizeof(Node4Rec));
+  out.swap(better);
+  *stack_need = std::max(need, 1);
+  opt->optimized = true;
+  opt->cost_out = cost;
   return 0;
 }
 

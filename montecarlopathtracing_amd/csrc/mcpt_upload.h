@@ -23,7 +23,9 @@ struct DeviceScene {
 
 // tris (n) and nodes (2n-1, the HLBVH layout) are DEVICE arrays; on failure
 // the arrays already allocated in *out are left for the caller to free.
+// sah_passes > 0: at or below kSahOptimizeMaxLeaves leaves the search tree is
+// the optimised one of build_sah4 (mcpt_bvh4.h), made by that host function.
 int build_scene_device(const mcpt_triangle *tris, int64_t n, const mcpt_bvh_node *nodes, int32_t n_mats,
-                       hipStream_t st, DeviceScene *out);
+                       int sah_passes, hipStream_t st, DeviceScene *out);
 
 }  // namespace mcpt

@@ -27,6 +27,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/mcpt_hip.h"
@@ -1019,8 +1020,11 @@ static int d2h(T *h, const T *d, size_t count, hipStream_t st) {
   return MCPT_OK;
 }
 
+static int sah_tree_device(int64_t m, hipStream_t st, Scratch &S, float *lbox, float *cen, int32_t *ltri, int32_t *idx,
+                           int32_t *own, DeviceScene *out);
+
 int build_scene_device(const mcpt_triangle *tris, int64_t n, const mcpt_bvh_node *nodes, int32_t n_mats,
-                       hipStream_t st, DeviceScene *out) {
+                       int sah_passes, hipStream_t st, DeviceScene *out) {
   std::memset(out, 0, sizeof(*out));
   if (n <= 0) return fail(MCPT_ERR_ARG, "scene_upload_device: no triangles");
   if (n > (int64_t)0x3FFFFFFF) return fail(MCPT_ERR_LIMIT, "scene_upload_device: too many triangles");
@@ -1140,19 +1144,79 @@ int build_scene_device(const mcpt_triangle *tris, int64_t n, const mcpt_bvh_node
   // ---- the SAH search tree over the reference's leaves
   const int64_t m = n;
   float *lbox = nullptr, *cen = nullptr;
-  int32_t *ltri = nullptr, *idx = nullptr, *idx2 = nullptr, *own = nullptr, *own2 = nullptr, *slot_of = nullptr;
-  SahNode *sn = nullptr;
+  int32_t *ltri = nullptr, *idx = nullptr, *own = nullptr;
   UP_OK(S.alloc(&lbox, 6 * m));
   UP_OK(S.alloc(&cen, 3 * m));
   UP_OK(S.alloc(&ltri, m));
   UP_OK(S.alloc(&idx, m));
-  UP_OK(S.alloc(&idx2, m));
   UP_OK(S.alloc(&own, m));
+  hipLaunchKernelGGL(k_leaf_init, dim3(nblk(m, 256)), dim3(256), 0, st, nodes, m, lbox, ltri, cen, idx, own);
+  UP_OK(hipGetLastError());
+  if (sah_passes > 0 && m <= kSahOptimizeMaxLeaves) {
+    // The optimised tree (mcpt_sah.cpp) is sequential host work: both upload
+    // paths call the one host function on the same leaves, so their bytes
+    // agree by construction.  The leaves go to the host (28 B each), the
+    // 128-B nodes come back; everything derived from them is built here as ever.
+    std::vector<float> hbox(6 * (size_t)m);
+    std::vector<int32_t> htri((size_t)m);
+    if (int rc = d2h(hbox.data(), lbox, 6 * (size_t)m, st)) return rc;
+    if (int rc = d2h(htri.data(), ltri, (size_t)m, st)) return rc;
+    std::vector<LeafRef> leaves((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+      std::memcpy(leaves[i].box, &hbox[6 * (size_t)i], sizeof(leaves[i].box));
+      leaves[i].tri = htri[i];
+    }
+    std::vector<Node4Rec> hnear;
+    int32_t need_h = 1;
+    SahOptimize opt;
+    opt.passes = sah_passes;
+    const unsigned hw = std::thread::hardware_concurrency();
+    if (build_sah4(leaves, hnear, &need_h, (int)std::min(16u, std::max(1u, hw)), &opt) != 0 || hnear.empty())
+      return fail(MCPT_ERR_ARG, "scene_upload_device: no leaves");
+    UP_OK(hipMalloc(&out->near4, hnear.size() * sizeof(Node4Rec)));
+    out->n_near4 = (int64_t)hnear.size();
+    UP_OK(hipMemcpyAsync(out->near4, hnear.data(), hnear.size() * sizeof(Node4Rec), hipMemcpyHostToDevice, st));
+    UP_OK(hipStreamSynchronize(st));  // `hnear` leaves scope
+    out->depth4 = std::max(out->depth4, need_h);
+  } else if (int rc = sah_tree_device(m, st, S, lbox, cen, ltri, idx, own, out)) {
+    return rc;
+  }
+  if (out->depth4 > 192) return fail(MCPT_ERR_LIMIT, "scene_upload: 4-wide stack too deep");
+  const Node4Rec *near = (const Node4Rec *)out->near4;
+  const int64_t nw = out->n_near4;
+
+  // the quantized tree, when every leaf box is its triangle's vertex bounds
+  if (int rc = d2h(&fl, flags, 1, st)) return rc;
+  out->quant = (fl & 64) == 0;
+  if (out->quant) {
+    UP_OK(hipMemsetAsync(flags, 0, 4, st));
+    UP_OK(hipMalloc(&out->near4q, nw * sizeof(Node4Q)));
+    hipLaunchKernelGGL(k_quantize, dim3(nblk(nw, 128)), dim3(128), 0, st, near, (int64_t)nw, (Node4Q *)out->near4q,
+                       flags);
+    UP_OK(hipGetLastError());
+    if (int rc = d2h(&fl, flags, 1, st)) return rc;
+    out->quant = fl == 0;
+  }
+  if (!out->quant) {
+    if (out->near4q) (void)hipFree(out->near4q);
+    if (out->triq) (void)hipFree(out->triq);
+    out->near4q = nullptr;
+    out->triq = nullptr;
+  }
+  UP_OK(hipStreamSynchronize(st));
+  return MCPT_OK;
+}
+
+// The plain SAH search tree over the m leaves k_leaf_init set up, built and
+// collapsed on the GPU: out->near4, n_near4, and its stack need into depth4.
+static int sah_tree_device(int64_t m, hipStream_t st, Scratch &S, float *lbox, float *cen, int32_t *ltri, int32_t *idx,
+                           int32_t *own, DeviceScene *out) {
+  int32_t *idx2 = nullptr, *own2 = nullptr, *slot_of = nullptr;
+  SahNode *sn = nullptr;
+  UP_OK(S.alloc(&idx2, m));
   UP_OK(S.alloc(&own2, m));
   UP_OK(S.alloc(&sn, 2 * m - 1));
   UP_OK(S.alloc(&slot_of, 2 * m - 1));
-  hipLaunchKernelGGL(k_leaf_init, dim3(nblk(m, 256)), dim3(256), 0, st, nodes, m, lbox, ltri, cen, idx, own);
-  UP_OK(hipGetLastError());
   UP_OK(hipMemsetAsync(slot_of, 0xFF, (2 * m - 1) * sizeof(int32_t), st));  // -1: not a large range
   {
     SahNode root;
@@ -1323,27 +1387,6 @@ int build_scene_device(const mcpt_triangle *tris, int64_t n, const mcpt_bvh_node
   int32_t need0 = 0;
   if (int rc = d2h(&need0, need, 1, st)) return rc;  // need_by_id[0]: the root's
   out->depth4 = std::max(out->depth4, std::max(need0, 1));
-  if (out->depth4 > 192) return fail(MCPT_ERR_LIMIT, "scene_upload: 4-wide stack too deep");
-
-  // the quantized tree, when every leaf box is its triangle's vertex bounds
-  if (int rc = d2h(&fl, flags, 1, st)) return rc;
-  out->quant = (fl & 64) == 0;
-  if (out->quant) {
-    UP_OK(hipMemsetAsync(flags, 0, 4, st));
-    UP_OK(hipMalloc(&out->near4q, nw * sizeof(Node4Q)));
-    hipLaunchKernelGGL(k_quantize, dim3(nblk(nw, 128)), dim3(128), 0, st, near, (int64_t)nw, (Node4Q *)out->near4q,
-                       flags);
-    UP_OK(hipGetLastError());
-    if (int rc = d2h(&fl, flags, 1, st)) return rc;
-    out->quant = fl == 0;
-  }
-  if (!out->quant) {
-    if (out->near4q) (void)hipFree(out->near4q);
-    if (out->triq) (void)hipFree(out->triq);
-    out->near4q = nullptr;
-    out->triq = nullptr;
-  }
-  UP_OK(hipStreamSynchronize(st));
   return MCPT_OK;
 }
 

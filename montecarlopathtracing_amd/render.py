@@ -153,6 +153,21 @@ class Renderer:
     def upload(self, data):
         return DeviceScene(self, data)
 
+    @staticmethod
+    def set_sah_optimize(passes=3):
+        """mcpt_set_sah_optimize: process-wide, for the scenes uploaded from
+        here on.  passes > 0 (default 3) optimises the search tree of scenes of
+        up to 131072 triangles by subtree reinsertion under the plain tree's
+        stack need; 0 or False keeps the plain tree.  Cost only, never results."""
+        L.check(L.lib().mcpt_set_sah_optimize(3 if passes is True else int(passes)))
+
+    @staticmethod
+    def sah_optimize():
+        """The passes mcpt_set_sah_optimize set (0: the plain tree)."""
+        p = ctypes.c_int32()
+        L.check(L.lib().mcpt_get_sah_optimize(ctypes.byref(p)))
+        return p.value
+
     def set_stats(self, on):
         L.check(L.lib().mcpt_set_stats(self.ctx, int(bool(on))))
         self._stats_on = bool(on)
