@@ -726,7 +726,8 @@ int mcpt_shading_normals(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *
  *     fma(w11, t11, fma(w01, t01, fma(w10, t10, w00 t00)))); a channel whose
  *     four texels are equal is that value exactly (the four fp32 weights sum
  *     to 1 only within an ulp, and a texture of ones must give 1.0f);
- *   Tex = (r, g, b, 1); an untextured triangle gives (1, 1, 1, 1) after one
+ *   Tex = (r, g, b, alpha) (alpha: 1 unless an alpha is set, see the cutouts
+ *     below); an untextured triangle gives (1, 1, 1, 1) after one
  *     16-B gather.
  * Shading: kd is replaced by kd * Tex, one multiply per lane, wherever the
  * diffuse lobe of MCPT_DIFFUSE and of MCPT_GLOSSY reads kd.  ks, a light's
@@ -794,6 +795,66 @@ int mcpt_mtl_maps_from_text(const char *text, int64_t len, char *names, int64_t 
 int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_textures *textures);
 int mcpt_texture_eval(mcpt_ctx *ctx, const mcpt_scene *scene, const int32_t *tri_ids_dev, const float *points_dev,
                       int64_t n, float *out_dev, void *stream);
+
+/* Opt-in alpha cutouts (MTL `map_d`, a texture's alpha channel; no reference
+ * counterpart).  Functions and one struct of their own: the
+ * ABI revision stays 5.
+ *
+ * Normative (fp32 on the device, csrc/mcpt_texture.h; float64 in
+ * tests/cutout_ref.py).
+ * Alpha in the texel pool: each texture of the scene's texture set may carry
+ *   an alpha image of its own size, values finite in [0, 1], row 0 the top,
+ *   stored in the .w of that texture's float4 texels; a texture without one
+ *   has .w = 1.0f in every texel (mcpt_scene_set_textures writes that).  The
+ *   scene holds one threshold a0 in (0, 1], default 0.5.
+ * Alpha at a hit: Tex.w of the texture lookup above is the same bilinear,
+ *   repeating lookup applied to .w, with the same weights and fma order; a
+ *   channel whose four texels are equal is that value exactly, so an opaque
+ *   texture gives exactly 1.0f; an untextured triangle gives 1.
+ * The cutout test is the first thing shading does with a hit of a live ray,
+ *   before the material switch and the depth cap, for every material type,
+ *   lights included.  A hit is cut when alpha < a0 and the path's pass count c
+ *   is below 255.  A cut hit does not shade: the ray goes on from the hit
+ *   point, o' = hit point, d' = d bit for bit; the colour, the seed, the depth
+ *   and the inside bits are unchanged; c' = c + 1 and no random number is
+ *   drawn.  With c == 255 the hit is shaded as if opaque: every path is finite
+ *   whatever the geometry.
+ * c lives in bits 8..15 of term_depth (origin.w), and the depth in bits 0..7,
+ *   while a scene has cutouts; a render or mcpt_shade call with max_depth >
+ *   255 on such a scene is MCPT_ERR_ARG.  A scene without cutouts keeps
+ *   MCPT_DEPTH_MASK's meaning.
+ * So a pass-through ray that then misses takes the environment as any miss
+ * does; the next segment starts with the usual tmin of 1e-3; mcpt_intersect is
+ * unchanged and reports the closest triangle, cut or not.
+ *
+ * mcpt_load_mtl_alpha_maps / mcpt_mtl_alpha_maps_from_text are
+ * mcpt_load_mtl_maps' twins for `map_d`: the same order, options, slashes and
+ * two-call pattern.
+ *
+ * mcpt_scene_set_texture_alpha(ctx, scene, a): a->alpha[i] is texture i's
+ * alpha image (its width * height floats) or NULL for an opaque texture.
+ * Validated before anything changes: MCPT_ERR_ARG, with the scene as it was,
+ * when the scene has no textures, n_textures is not its texture set's count,
+ * a value is outside [0, 1] or not finite, or the threshold is outside (0, 1].
+ * a NULL clears: every .w is 1 again and the depth keeps MCPT_DEPTH_MASK.  The
+ * call waits for work enqueued on the scene's GPU and drops the context's
+ * primary-hit cache, as mcpt_scene_set_textures does; a later
+ * mcpt_scene_set_textures (set or clear) drops the alpha.
+ *
+ * With an alpha set, the primary-hit cache's texture factor holds the primary
+ * hit's alpha in .w, so a cached first segment passes through exactly as a
+ * traced one does; mcpt_texture_eval's fourth lane is the alpha (1.0f
+ * without one).                                                            */
+typedef struct mcpt_texture_alpha {
+  int32_t n_textures;
+  const float *const *alpha; /* n_textures pointers, NULL: opaque */
+  float threshold;
+  float pad;
+} mcpt_texture_alpha;
+int mcpt_load_mtl_alpha_maps(const char *directory, const char *objname, char *names, int64_t *n_bytes,
+                             int64_t *n_materials);
+int mcpt_mtl_alpha_maps_from_text(const char *text, int64_t len, char *names, int64_t *n_bytes, int64_t *n_materials);
+int mcpt_scene_set_texture_alpha(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_texture_alpha *a);
 
 /* Opt-in bump and normal maps (MTL `map_Bump`, `bump`, `norm`; no reference
  * counterpart).  The reference, and a scene without maps,

@@ -3,7 +3,7 @@ or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
 
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
         [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]] [--smooth [DEG]]
-        [--textures] [--bump [SCALE]] [--aperture R (--focus F | --focus-at X,Y)]
+        [--textures] [--cutouts [THRESHOLD]] [--bump [SCALE]] [--aperture R (--focus F | --focus-at X,Y)]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -40,6 +40,10 @@ def parser():
     ap.add_argument("--textures", action="store_true",
                     help="the model's diffuse texture maps (OBJ vt, MTL map_Kd), even if the config entry has no "
                          "\"textures\" key")
+    ap.add_argument("--cutouts", nargs="?", type=float, const=True, default=None, metavar="THRESHOLD",
+                    help="alpha cutouts (MTL map_d, a map_Kd image's alpha channel): a hit whose alpha is below "
+                         "THRESHOLD (default 0.5, in (0, 1]) lets the ray through; switches --textures on, even if the "
+                         "config entry has no \"cutouts\" key")
     ap.add_argument("--bump", nargs="?", type=float, const=True, default=None, metavar="SCALE",
                     help="the model's bump and normal maps (MTL map_Bump, bump, norm); SCALE: factor on a height "
                          "map's per-texel slopes (default 1), even if the config entry has no \"bump\" key")
@@ -81,6 +85,12 @@ def cli_bump(a, cfg):
     """The height-map scale a run maps with, or None: --bump [SCALE] if given, else the entry's "bump"."""
     from . import config as C
     return cfg.BUMP() if a.bump is None else C.parse_bump(a.bump)
+
+
+def cli_cutouts(a, cfg):
+    """The alpha threshold a run cuts with, or None: --cutouts [THRESHOLD] if given, else the entry's "cutouts"."""
+    from . import config as C
+    return cfg.CUTOUTS() if a.cutouts is None else C.parse_cutouts(a.cutouts)
 
 
 def cli_smooth(a, cfg):
@@ -141,7 +151,7 @@ def main(argv=None):
     from .app import App
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
               denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth,
-              textures=True if a.textures else None, lens=cli_lens(a), bump=a.bump)
+              textures=True if a.textures else None, lens=cli_lens(a), bump=a.bump, cutouts=a.cutouts)
     if app.lens_spec is not None:
         print("lens: jitter switched on (a lens needs a fresh primary ray every frame)")
     t0 = time.time()
@@ -190,7 +200,7 @@ def _main_dist(a):
     env = cli_environment(a, cfg)
     apply_environment(rnd, sc, cfg.ENVIRONMENT() if env is None else C.parse_environment(env), cfg, root)
     apply_smooth(rnd, sc, cli_smooth(a, cfg), cfg, root)  # and shades with its own copy of the vertex normals
-    textured = apply_textures(rnd, sc, a.textures or cfg.TEXTURES(), cfg, root)  # and of the textures
+    textured = apply_textures(rnd, sc, a.textures or cfg.TEXTURES(), cfg, root, cli_cutouts(a, cfg))  # and of the textures, with their alpha
     apply_bump(rnd, sc, cli_bump(a, cfg), cfg, root)  # and of the bump and normal maps
     w, h = cfg.WIDTH(), cfg.HEIGHT()
     frames = a.frames or cfg.MAXATTEPMT() + 1

@@ -79,6 +79,12 @@ class Textures(ctypes.Structure):
                 ("images", ctypes.c_void_p)]
 
 
+class TextureAlpha(ctypes.Structure):
+    """mcpt_texture_alpha: n_textures, alpha (n_textures host float32 pointers, NULL: opaque), threshold, pad."""
+    _fields_ = [("n_textures", ctypes.c_int32), ("alpha", ctypes.c_void_p), ("threshold", ctypes.c_float),
+                ("pad", ctypes.c_float)]
+
+
 class NormalMapImage(ctypes.Structure):
     """mcpt_normal_map_image: xyz (host float32, width * height * 3), width, height."""
     _fields_ = [("xyz", ctypes.c_void_p), ("width", ctypes.c_int32), ("height", ctypes.c_int32)]
@@ -140,6 +146,9 @@ SIGNATURES = {
     "mcpt_mtl_maps_from_text": (_I32, [_P, _I64, _P, _P, _P]),
     "mcpt_scene_set_textures": (_I32, [_P, _P, _P]),
     "mcpt_texture_eval": (_I32, [_P, _P, _P, _P, _I64, _P, _P]),
+    "mcpt_load_mtl_alpha_maps": (_I32, [_S, _S, _P, _P, _P]),
+    "mcpt_mtl_alpha_maps_from_text": (_I32, [_P, _I64, _P, _P, _P]),
+    "mcpt_scene_set_texture_alpha": (_I32, [_P, _P, _P]),
     "mcpt_load_mtl_bump_maps": (_I32, [_S, _S, _P, _P, _P, _P, _P]),
     "mcpt_mtl_bump_maps_from_text": (_I32, [_P, _I64, _P, _P, _P, _P, _P]),
     "mcpt_scene_set_normal_maps": (_I32, [_P, _P, _P]),

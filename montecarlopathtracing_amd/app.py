@@ -46,6 +46,14 @@ shades every hit with its normal perturbed by the model's normal map (MTL
 the scale) at the hit's `vt` coordinates (Renderer.set_normal_maps).  The
 denoise pass's guide follows: first_hits returns the mapped normals.
 
+Extension: "cutouts": true | <threshold in (0, 1]> (App(..., cutouts=...),
+--cutouts [THRESHOLD]) cuts every hit whose texture alpha (the material's MTL
+`map_d` image, else the `map_Kd` image's own alpha channel) is below the
+threshold, default 0.5: the ray goes on through the hole
+(Renderer.set_texture_alpha).  It switches the textures on.  The scalars `d`
+and `Tr` are not honoured.  The denoise pass's guide and a lens' autofocus see
+through the holes: first_hits returns the first hit that is not cut.
+
 Extension: "lens": {"aperture": R, "focus": F} or {"aperture": R, "focus_at":
 [px, py]} (App(..., lens={...} or (R, F)), --aperture with --focus or
 --focus-at) renders through a thin lens of radius R focused at distance F
@@ -113,21 +121,29 @@ def apply_smooth(renderer, scene, crease, cfg, root):
     renderer.set_vertex_normals(scene, S.smooth_normals(scene.data.tris, crease, authored))
 
 
-def apply_textures(renderer, scene, on, cfg, root):
+def apply_textures(renderer, scene, on, cfg, root, cutouts=None):
     """Set a config entry's model textures (OBJ vt, MTL map_Kd) on an uploaded
-    scene when `on`; returns whether the scene is textured now.  App.init and
-    every rank of the multi-GPU CLI go through this."""
-    if not on:
+    scene when `on`; returns whether the scene is textured now.  `cutouts`
+    (config.parse_cutouts' threshold, or None) switches them on too and sets
+    the model's alpha (MTL map_d, a map_Kd image's alpha channel) with that
+    threshold.  App.init and every rank of the multi-GPU CLI go through this."""
+    if not on and cutouts is None:
         return False
     directory = os.path.join(root, cfg.GETDIRECTORY())
     if not directory.endswith("/"):
         directory += "/"
     tris = scene.data.tris
     mat_index = np.ascontiguousarray(tris["normal"][:, 3]).view(np.int32)  # pack_triangles put it there
-    uv, tri_tex, images = S.load_textures(directory, cfg.GETOBJNAME(), scene.data.mats, mat_index)
+    alphas = None
+    if cutouts is None:
+        uv, tri_tex, images = S.load_textures(directory, cfg.GETOBJNAME(), scene.data.mats, mat_index)
+    else:
+        uv, tri_tex, images, alphas = S.load_cutouts(directory, cfg.GETOBJNAME(), scene.data.mats, mat_index)
     if not (tri_tex >= 0).any():
         return False
     renderer.set_textures(scene, uv, tri_tex, images)
+    if alphas is not None and any(a is not None for a in alphas):
+        renderer.set_texture_alpha(scene, alphas, cutouts)
     return True
 
 
@@ -165,7 +181,7 @@ def resolve_lens(renderer, scene, camera, width, height, spec):
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
                  material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None,
-                 lens=None, bump=None):
+                 lens=None, bump=None, cutouts=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -200,6 +216,10 @@ class App:
         self.textured = False
         self.bump = self.cfg.BUMP() if bump is None else C.parse_bump(bump)  # None: the entry's "bump" key
         self.mapped = False
+        # None: the entry's "cutouts" key; else that key's value (True / False / threshold).  Cutouts switch textures on.
+        self.cutouts = self.cfg.CUTOUTS() if cutouts is None else C.parse_cutouts(cutouts)
+        if self.cutouts is not None:
+            self.textures = True
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -220,7 +240,7 @@ class App:
         self.scene = self.renderer.upload(self.data)
         apply_environment(self.renderer, self.scene, self.environment, self.cfg, self.root)
         apply_smooth(self.renderer, self.scene, self.smooth, self.cfg, self.root)
-        self.textured = apply_textures(self.renderer, self.scene, self.textures, self.cfg, self.root)
+        self.textured = apply_textures(self.renderer, self.scene, self.textures, self.cfg, self.root, self.cutouts)
         self.mapped = apply_bump(self.renderer, self.scene, self.bump, self.cfg, self.root)
         self.state = self.renderer.new_state(self.w, self.h, self.seeds)
         self.lens = resolve_lens(self.renderer, self.scene, self.camera, self.w, self.h, self.lens_spec)

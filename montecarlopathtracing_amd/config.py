@@ -81,6 +81,19 @@ def parse_textures(v):
     return v
 
 
+def parse_cutouts(v):
+    """The "cutouts" extension key of a config entry -> the alpha threshold in
+    (0, 1] of the model's cutouts (true: 0.5), or None (false: opaque textures)."""
+    if isinstance(v, bool):
+        return 0.5 if v else None
+    if not isinstance(v, (int, float)):
+        raise ValueError('config "cutouts" must be true, false or a threshold in (0, 1], got %r' % (v,))
+    v = float(v)
+    if not (v > 0.0 and v <= 1.0):
+        raise ValueError('config "cutouts" must be a threshold in (0, 1], got %r' % (v,))
+    return v
+
+
 def parse_lens(v):
     """The "lens" extension key of a config entry ->
     {"aperture": R, "focus": F or None, "focus_at": (px, py) or None}.
@@ -195,6 +208,9 @@ class Config:
         # "bump": true | <scale > 0>: the model's bump and normal maps (MTL map_Bump,
         # bump, norm; Renderer.set_normal_maps); None: the unmapped normals
         self.bump = parse_bump(c["bump"]) if "bump" in c else None
+        # "cutouts": true | <threshold in (0, 1]>: the model's alpha cutouts (MTL map_d, a map_Kd image's
+        # alpha channel; Renderer.set_texture_alpha), which take the textures with them; None: opaque
+        self.cutouts = parse_cutouts(c["cutouts"]) if "cutouts" in c else None
         # "lens": {"aperture": R, "focus": F | "focus_at": [px, py]}: a thin-lens
         # camera (depth of field; Renderer.render_frames' lens); None: the pinhole
         self.lens = parse_lens(c["lens"]) if "lens" in c else None
@@ -244,4 +260,5 @@ class Config:
     def SMOOTH(self): return self.smooth  # extension: smooth shading's crease angle in degrees, or None
     def LENS(self): return self.lens  # extension: parse_lens' dict (thin-lens camera), or None
     def TEXTURES(self): return self.textures  # extension: the model's map_Kd textures on the diffuse lobe
+    def CUTOUTS(self): return self.cutouts  # extension: the alpha threshold of the model's cutouts (textures on), or None
     def BUMP(self): return self.bump  # extension: the height maps' slope scale of the model's bump and normal maps, or None

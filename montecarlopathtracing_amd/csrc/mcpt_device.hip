@@ -55,6 +55,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <array>
 #include <vector>
 
 #include "../../include/mcpt_hip.h"
@@ -219,6 +220,12 @@ struct mcpt_scene {
   TexRec *texrec = nullptr, *texrec4 = nullptr;
   f4 *texels = nullptr;
   int64_t n_texels = 0;
+  // mcpt_scene_set_texture_alpha: cutouts.  The alpha lives in the texels' .w
+  // (1.0f without one); cut_a0 is the threshold, 0: none set, and the depth
+  // keeps all of MCPT_DEPTH_MASK.  tex_dims: each texture's pool offset, width
+  // and height (host), which the alpha setter needs.  A set or clear bumps vn_epoch too.
+  float cut_a0 = 0.0f;
+  std::vector<std::array<int64_t, 3>> tex_dims;
   // mcpt_scene_set_normal_maps: bump and normal maps.  bumprec in the order of
   // tris and triq, bumprec4 in tri4's, bump_texels the one pool all records
   // point into; all null: the shading normal is the unmapped one, by the
@@ -719,11 +726,17 @@ __device__ inline void jitter_draw(uint32_t &seed, float &jx, float &jy) {
 }
 
 // -------------------------------------------------------------------- shade
+// A scene with cutouts counts a path's cut hits in term_depth bits 8..15
+constexpr uint32_t kCutCountMask = 0x0000FF00u, kCutCountOne = 0x00000100u;
+// the cutout test (shade_hit): alpha below the threshold (0: no cutouts, never) and fewer than 255 passes so far
+__device__ inline bool cutout_cut(float alpha, float a0, int32_t term_depth) {
+  return alpha < a0 && (term_depth & (int32_t)kCutCountMask) != (int32_t)kCutCountMask;
+}
 struct ShadeIn {
   f4 o, d;       // ray (o.w = term_depth bits, d.w = id bits)
   f4 nrm;        // hit normal (flipped to face the ray)
   f4 pt;         // hit point
-  int32_t mat;
+  int32_t mat;   // (the textured forms: < 0, ~material, marks a cut hit)
 };
 struct ShadeOut {
   f4 o, d;
@@ -747,13 +760,35 @@ struct ShadeOut {
 // TX: the scene has textures: kd is the material's times `tex`
 // (texture_factor of the hit, mcpt_texture.h) wherever it is read; nothing
 // else changes and no draw is added.
+// a0 (TX forms, launch-uniform): the scene's cutout threshold
+// (mcpt_scene_set_texture_alpha), 0: no cutouts.  With one, the first thing a
+// hit meets: a cut (cutout_cut of the hit's alpha: tex.w < a0 and a pass count,
+// term_depth bits 8..15, below 255) lets the ray go on from the hit point in
+// its direction, the count one up, with the colour, the seed, the depth and
+// the inside bits it had and no draw; the depth is then bits 0..7.  The caller
+// decides it where the lookup ends and hands it over as in.mat < 0 (~material;
+// a cut hit's material is never read, and ids are never negative), so neither
+// the alpha nor a lane mask stays live across the normal map's lookup: the
+// forms at the register cap keep their registers.  A cut is decided by the hit
+// alone, so a hit that is shaded again after a rejected lobe sample is not cut
+// then either.
 template <bool G = true, class Mat = const mcpt_material, bool TX = false>
 __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, f4 color, uint32_t &seed,
-                                     int max_depth, bool &resample, f4 tex = (f4){1.0f, 1.0f, 1.0f, 1.0f}) {
+                                     int max_depth, bool &resample, f4 tex = (f4){1.0f, 1.0f, 1.0f, 1.0f},
+                                     float a0 = 0.0f) {
   ShadeOut r;
   r.bad = false;
   r.new_ray = true;
   r.pending = false;
+  if constexpr (TX) {
+    if (in.mat < 0) {
+      r.o = in.pt;
+      r.o.w = as_f(as_i(in.o.w) + (int32_t)kCutCountOne);
+      r.d = in.d;
+      r.color = color;
+      return r;
+    }
+  }
   // material fields are read where they are used (the table is in LDS): the
   // draw below keeps fewer values live
   Mat *__restrict__ Mp = mats + in.mat;
@@ -849,7 +884,9 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
       return r;
   }
   int32_t ntd = as_i(no.w);
-  if ((ntd & 0x0000FFFF) >= max_depth) {
+  int32_t depth = ntd & 0x0000FFFF;
+  if constexpr (TX) depth = ntd & (a0 > 0.0f ? 0x000000FF : 0x0000FFFF);  // cutouts: bits 8..15 count the passes
+  if (depth >= max_depth) {
     color = (f4){0.0f, 0.0f, 0.0f, 0.0f};
     no.w = as_f(ntd | (int32_t)MCPT_TERMINATED);
   }
@@ -861,11 +898,14 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
 // the whole of shade.cl's work for one ray (the wavefront kernel)
 template <bool TX = false>
 __device__ inline ShadeOut shade_hit_full(const mcpt_material *__restrict__ mats, const ShadeIn &in, f4 color,
-                                          uint32_t &seed, int max_depth, f4 tex = (f4){1.0f, 1.0f, 1.0f, 1.0f}) {
+                                          uint32_t &seed, int max_depth, f4 tex = (f4){1.0f, 1.0f, 1.0f, 1.0f},
+                                          float a0 = 0.0f) {
   bool resample = false;
+  ShadeIn hit = in;
+  if (TX && cutout_cut(tex.w, a0, as_i(in.o.w))) hit.mat = ~hit.mat;  // cut: shade_hit's in.mat < 0
   ShadeOut so;
   do {
-    so = shade_hit<true, const mcpt_material, TX>(mats, in, color, seed, max_depth, resample, tex);
+    so = shade_hit<true, const mcpt_material, TX>(mats, hit, color, seed, max_depth, resample, tex, a0);
   } while (so.pending);
   return so;
 }
@@ -993,6 +1033,7 @@ struct RenderArgs {
   const f4 *prim_tex;         // textured launches that read A.prim: each pixel's primary-hit texture factor (k_primary_tex)
   float lens_radius, lens_focus;  // jittered launches: the thin lens (mcpt_lens.h), radius 0: none (last, like vnrm)
   BumpView bump;              // mapped launches: the scene's normal-map records, indexed like S.tris, and their texel pool (last, likewise)
+  float cut_a0;               // textured launches: the scene's cutout threshold (shade_hit's a0), 0: no cutouts (last, likewise)
 };
 
 constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193, scenebuild.cpp:125)
@@ -1619,7 +1660,10 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
             const int32_t hw = as_i(tn.w);
             if (hw >= 0) {  // a cached primary hit: the finished shading normal and the material
               in.mat = hw;
-              if constexpr (TX) tex = A.prim_tex[pixel_id<size_t>(pxy, A.W)];  // and its texture factor
+              if constexpr (TX) {  // and its texture factor, the alpha in .w
+                tex = A.prim_tex[pixel_id<size_t>(pxy, A.W)];
+                if (cutout_cut(tex.w, A.cut_a0, as_i(o.w))) in.mat = ~in.mat;  // cut: decided as soon as the alpha is there
+              }
             } else {  // traced: the triangle's rows, material and vertex normals (the index checked in MCPT_DEBUG builds)
               const int32_t ti = MCPT_DCHECK(~hw < S.n_tris, 2) ? ~hw : 0;
               if constexpr (TX) {  // the triangle's rows (v0, nab, nac) once, for the normal and the texture
@@ -1642,9 +1686,11 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
                 }
                 if constexpr (BM) {
                   if (A.tex.rec) tex = texture_factor<kDebug>(A.tex, ti, r0, r1, r2, in.pt, &A.stats[kTexDebugSlot]);
+                  if (cutout_cut(tex.w, A.cut_a0, as_i(o.w))) in.mat = ~in.mat;
                   in.nrm = bump_normal<kDebug>(A.bump, ti, r0, r1, r2, tn.xyz, in.pt, d, in.nrm, &A.stats[kBumpDebugSlot]);
                 } else {
                   tex = texture_factor<kDebug>(A.tex, ti, r0, r1, r2, in.pt, &A.stats[kTexDebugSlot]);
+                  if (cutout_cut(tex.w, A.cut_a0, as_i(o.w))) in.mat = ~in.mat;
                 }
               } else if constexpr (Q) {
                 const DevTriQ &T = S.triq[ti];
@@ -1667,9 +1713,9 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
           ShadeOut so;
           if constexpr (TX) {
             if (A.lds_mats)
-              so = shade_hit<G, LdsMaterial, true>(lds_mat_table, in, color, seed, A.max_depth, rs, tex);
+              so = shade_hit<G, LdsMaterial, true>(lds_mat_table, in, color, seed, A.max_depth, rs, tex, A.cut_a0);
             else
-              so = shade_hit<G, const mcpt_material, true>(S.mats, in, color, seed, A.max_depth, rs, tex);
+              so = shade_hit<G, const mcpt_material, true>(S.mats, in, color, seed, A.max_depth, rs, tex, A.cut_a0);
           } else if (A.lds_mats)  // LDS-typed reads (ds_read, no flat access waiting on vector memory)
             so = shade_hit<G>(lds_mat_table, in, color, seed, A.max_depth, rs);
           else
@@ -2101,7 +2147,7 @@ __global__ void __launch_bounds__(1024) k_tile_sort(const uint8_t *keys, int32_t
 template <bool TX>
 __device__ __forceinline__ void shade_one(const mcpt_material *mats, mcpt_ray *rays, const mcpt_hit *hits, f4 *colors,
                                           uint32_t *seeds, int64_t n, int max_depth, const EnvView &env, int env_on,
-                                          const DevTri *tris, int64_t n_tris, const TexView &tv) {
+                                          const DevTri *tris, int64_t n_tris, const TexView &tv, float a0) {
   int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n) return;
   mcpt_ray &R = rays[id];
@@ -2130,7 +2176,7 @@ __device__ __forceinline__ void shade_one(const mcpt_material *mats, mcpt_ray *r
       const f4 v0 = T.v0, nab = T.nab, nac = T.nac;
       tex = texture_factor(tv, ti, v0.xyz, nab.xyz, nac.xyz, in.pt);
     }
-    so = shade_hit_full<true>(mats, in, colors[id], seed, max_depth, tex);
+    so = shade_hit_full<true>(mats, in, colors[id], seed, max_depth, tex, a0);
   } else {
     so = shade_hit_full(mats, in, colors[id], seed, max_depth);
   }
@@ -2146,12 +2192,12 @@ __device__ __forceinline__ void shade_one(const mcpt_material *mats, mcpt_ray *r
 }
 __global__ void k_shade(const mcpt_material *mats, mcpt_ray *rays, const mcpt_hit *hits, f4 *colors,
                         uint32_t *seeds, int64_t n, int max_depth, EnvView env, int env_on) {
-  shade_one<false>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, nullptr, 0, TexView{});
+  shade_one<false>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, nullptr, 0, TexView{}, 0.0f);
 }
 __global__ void k_shade_tex(const mcpt_material *mats, mcpt_ray *rays, const mcpt_hit *hits, f4 *colors,
                             uint32_t *seeds, int64_t n, int max_depth, EnvView env, int env_on, const DevTri *tris,
-                            int64_t n_tris, TexView tv) {
-  shade_one<true>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, tris, n_tris, tv);
+                            int64_t n_tris, TexView tv, float a0) {
+  shade_one<true>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, tris, n_tris, tv, a0);
 }
 
 __global__ void k_accumulate(f4 *colors, f4 *hist, int32_t *count, int64_t n, int max_attempt) {
@@ -3335,10 +3381,12 @@ int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_texture
   // validate everything before anything changes: a failed call leaves the scene's textures as they were
   std::vector<TexRec> rec;
   std::vector<f4> pool;
+  std::vector<int64_t> dims_base;  // each texture's first texel in the pool
   if (tx) {
     if (!tx->uv || !tx->tri_tex || tx->n_textures < 0 || (tx->n_textures > 0 && !tx->images))
       return mcpt::fail(MCPT_ERR_ARG, "set_textures: null uv, tri_tex or images");
-    std::vector<int64_t> base((size_t)tx->n_textures);
+    std::vector<int64_t> &base = dims_base;
+    base.resize((size_t)tx->n_textures);
     int64_t total = 0;
     for (int32_t k = 0; k < tx->n_textures; ++k) {
       const mcpt_texture_image &im = tx->images[k];
@@ -3366,7 +3414,7 @@ int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_texture
         const float r = im.rgb[3 * j], g = im.rgb[3 * j + 1], b = im.rgb[3 * j + 2];
         if (!(r >= 0.0f && r < INFINITY && g >= 0.0f && g < INFINITY && b >= 0.0f && b < INFINITY))
           return mcpt::fail(MCPT_ERR_ARG, "set_textures: texture " + std::to_string(k) + " has a negative or non-finite texel");
-        pool[(size_t)(base[(size_t)k] + j)] = (f4){r, g, b, 0.0f};
+        pool[(size_t)(base[(size_t)k] + j)] = (f4){r, g, b, 1.0f};  // opaque until an alpha is set
       }
     }
     rec.resize((size_t)n);
@@ -3413,7 +3461,62 @@ int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_texture
   for (void *p : {(void *)scene->texrec, (void *)scene->texrec4, (void *)scene->texels})
     if (p) (void)hipFree(p);
   scene->texrec = a, scene->texrec4 = a4, scene->texels = px, scene->n_texels = tx ? (int64_t)pool.size() : 0;
+  scene->cut_a0 = 0.0f;  // a new texture set (or none) has no alpha
+  scene->tex_dims.clear();
+  for (int32_t k = 0; tx && k < tx->n_textures; ++k)
+    scene->tex_dims.push_back({dims_base[(size_t)k], (int64_t)tx->images[k].width, (int64_t)tx->images[k].height});
   ++scene->vn_epoch;  // the primary-hit records of any context are those of another scene now
+  ctx->prim_valid = false;
+  return MCPT_OK;
+}
+
+// The alpha of a scene's textures (cutouts): one float per pool texel into the
+// texels' .w, on the device; nothing else of a texel is touched.
+__global__ void __launch_bounds__(256) k_set_texel_alpha(f4 *__restrict__ texels, const float *__restrict__ alpha, int64_t n) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k < n) texels[k].w = alpha[k];
+}
+
+int mcpt_scene_set_texture_alpha(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_texture_alpha *al) {
+  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: null context or scene");
+  if (ctx->device != scene->device)
+    return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: scene and context are on different GPUs");
+  if (!scene->texrec) return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: the scene has no textures");
+  // validate everything before anything changes: a failed call leaves the scene as it was
+  const int64_t total = scene->n_texels;
+  std::vector<float> w((size_t)total, 1.0f);
+  if (al) {
+    if (al->n_textures != (int32_t)scene->tex_dims.size() || (al->n_textures > 0 && !al->alpha))
+      return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: n_textures is not the texture set's count, or null alpha");
+    if (!(al->threshold > 0.0f && al->threshold <= 1.0f))
+      return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: threshold outside (0, 1]");
+    for (int32_t k = 0; k < al->n_textures; ++k) {
+      const float *a = al->alpha[k];
+      if (!a) continue;
+      const std::array<int64_t, 3> &d = scene->tex_dims[(size_t)k];
+      const int64_t m = d[1] * d[2];
+      if (d[0] + m > total) return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: texture outside the pool");
+      for (int64_t j = 0; j < m; ++j) {
+        if (!(a[j] >= 0.0f && a[j] <= 1.0f))
+          return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: texture " + std::to_string(k) + " has an alpha outside [0, 1] or not finite");
+        w[(size_t)(d[0] + j)] = a[j];
+      }
+    }
+  }
+  HIP_OK(hipSetDevice(scene->device));
+  HIP_OK(hipDeviceSynchronize());  // renders already enqueued may still read the texels
+  float *dw = nullptr;
+  HIP_OK(hipMalloc((void **)&dw, (size_t)total * sizeof(float)));
+  hipError_t e = hipMemcpy(dw, w.data(), (size_t)total * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_set_texel_alpha, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, scene->texels, dw, total);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  (void)hipFree(dw);
+  if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string("set_texture_alpha: ") + hipGetErrorString(e));
+  scene->cut_a0 = al ? al->threshold : 0.0f;
+  ++scene->vn_epoch;  // the primary-hit records hold the factor's .w: they are another scene's now
   ctx->prim_valid = false;
   return MCPT_OK;
 }
@@ -3867,6 +3970,8 @@ int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_c
   MCPT_TRY(check_lens(lens, "render"));
   const bool lens_on = lens && lens->radius > 0.0f;
   if (lens_on && p->jitter != 1) return mcpt::fail(MCPT_ERR_ARG, "render: a lens needs params->jitter = 1");
+  if (scene->cut_a0 > 0.0f && p->max_depth > 255)
+    return mcpt::fail(MCPT_ERR_ARG, "render: max_depth above 255 on a scene with cutouts");
   HIP_OK(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
   RenderArgs A;
@@ -3876,6 +3981,7 @@ int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_c
   A.vnrm = scene->vnrm;
   A.tex = TexView{scene->texrec, scene->texels, scene->n_texels};
   A.bump = BumpView{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
+  A.cut_a0 = scene->cut_a0;
   A.lens_radius = lens_on ? lens->radius : 0.0f, A.lens_focus = lens_on ? lens->focus_distance : 1.0f;
   A.seeds = seeds;
   A.hist = (f4 *)hist;
@@ -4021,12 +4127,14 @@ int mcpt_shade(mcpt_ctx *ctx, const mcpt_scene *scene, mcpt_ray *rays, const mcp
                uint32_t *seeds, int64_t n, int32_t max_depth, void *stream) {
   if (!ctx || !scene || !rays || !hits || !color || !seeds || n < 0 || max_depth <= 0)
     return mcpt::fail(MCPT_ERR_ARG, "shade: bad argument");
+  if (scene->cut_a0 > 0.0f && max_depth > 255)
+    return mcpt::fail(MCPT_ERR_ARG, "shade: max_depth above 255 on a scene with cutouts");
   if (n == 0) return MCPT_OK;
   HIP_OK(hipSetDevice(ctx->device));
   if (scene->texrec)
     hipLaunchKernelGGL(k_shade_tex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene->mats,
                        rays, hits, (f4 *)color, seeds, n, max_depth, scene->env, scene->env_on ? 1 : 0, scene->tris,
-                       scene->n_tris, TexView{scene->texrec, scene->texels, scene->n_texels});
+                       scene->n_tris, TexView{scene->texrec, scene->texels, scene->n_texels}, scene->cut_a0);
   else
     hipLaunchKernelGGL(k_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene->mats, rays,
                        hits, (f4 *)color, seeds, n, max_depth, scene->env, scene->env_on ? 1 : 0);

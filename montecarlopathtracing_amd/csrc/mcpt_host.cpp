@@ -1107,8 +1107,9 @@ std::string map_name(const char *q, const char *eol, double *bm = nullptr) {
   }
 }
 
-// parse_mtl's records, their map_Kd names alone (the same order: one per newmtl)
-void parse_mtl_maps(const char *p, const char *end, std::vector<std::string> *maps) {
+// parse_mtl's records, their map_Kd names alone (the same order: one per
+// newmtl); `word`: another map statement's instead (map_d, the cutouts')
+void parse_mtl_maps(const char *p, const char *end, std::vector<std::string> *maps, const char *word = "map_Kd") {
   bool have = false;
   while (p < end) {
     const char *eol = (const char *)std::memchr(p, '\n', end - p);
@@ -1119,7 +1120,7 @@ void parse_mtl_maps(const char *p, const char *end, std::vector<std::string> *ma
     if (k == "newmtl") {
       maps->push_back(std::string());
       have = true;
-    } else if (k == "map_Kd" && have) {
+    } else if (k == word && have) {
       maps->back() = map_name(q, eol);
     }
     p = eol + 1;
@@ -1231,8 +1232,10 @@ extern "C" int mcpt_mtl_maps_from_text(const char *text, int64_t len, char *name
   return emit_maps(maps, names, n_bytes, n_materials);
 }
 
-extern "C" int mcpt_load_mtl_maps(const char *directory, const char *objname, char *names, int64_t *n_bytes,
-                                  int64_t *n_materials) {
+namespace {
+// mcpt_load_mtl_maps for the map statement `word`
+int load_mtl_maps_of(const char *word, const char *directory, const char *objname, char *names, int64_t *n_bytes,
+                     int64_t *n_materials) {
   if (!directory || !objname || !n_bytes || !n_materials) return fail(MCPT_ERR_ARG, "load_mtl_maps: null argument");
   std::string dir(directory), text;
   if (!read_file(dir + objname, &text)) return fail(MCPT_ERR_IO, "load_mtl_maps: cannot read " + dir + objname);
@@ -1250,7 +1253,7 @@ extern "C" int mcpt_load_mtl_maps(const char *directory, const char *objname, ch
         if (t.p == t.e) break;
         std::string mt;
         if (read_file(dir + std::string(t.p, t.e), &mt)) {
-          parse_mtl_maps(mt.data(), mt.data() + mt.size(), &maps);
+          parse_mtl_maps(mt.data(), mt.data() + mt.size(), &maps, word);
           break;
         }
       }
@@ -1258,6 +1261,26 @@ extern "C" int mcpt_load_mtl_maps(const char *directory, const char *objname, ch
     p = eol + 1;
   }
   return emit_maps(maps, names, n_bytes, n_materials);
+}
+}  // namespace
+
+extern "C" int mcpt_load_mtl_maps(const char *directory, const char *objname, char *names, int64_t *n_bytes,
+                                  int64_t *n_materials) {
+  return load_mtl_maps_of("map_Kd", directory, objname, names, n_bytes, n_materials);
+}
+
+// ------------------------------------------------ alpha cutouts (opt-in): map_d
+extern "C" int mcpt_mtl_alpha_maps_from_text(const char *text, int64_t len, char *names, int64_t *n_bytes,
+                                             int64_t *n_materials) {
+  if (!n_bytes || !n_materials || len < 0 || (len > 0 && !text)) return fail(MCPT_ERR_ARG, "mtl_alpha_maps: bad argument");
+  std::vector<std::string> maps;
+  parse_mtl_maps(text, text + len, &maps, "map_d");
+  return emit_maps(maps, names, n_bytes, n_materials);
+}
+
+extern "C" int mcpt_load_mtl_alpha_maps(const char *directory, const char *objname, char *names, int64_t *n_bytes,
+                                        int64_t *n_materials) {
+  return load_mtl_maps_of("map_d", directory, objname, names, n_bytes, n_materials);
 }
 
 // ------------------------------------------- bump and normal maps (opt-in)

@@ -24,7 +24,8 @@ struct __attribute__((aligned(16))) TexRec {
 static_assert(sizeof(TexRec) == 32, "32-B texture record");
 
 // What a kernel needs of a scene's textures: the records and the one pool of
-// float4 texels (rgb, .w unused; each texture's rows top first).
+// float4 texels (rgb, .w the alpha of mcpt_scene_set_texture_alpha, 1.0f
+// without one; each texture's rows top first).
 struct TexView {
   const TexRec *rec;
   const f4 *texels;
@@ -32,7 +33,9 @@ struct TexView {
 };
 
 #ifdef __HIPCC__
-// kd's factor at point pt (xyz) on the triangle whose rows are v0, nab = -(v1 -
+// kd's factor (xyz) and the cutout alpha (.w: the same bilinear, repeating
+// lookup on the texels' .w, the same weights and fma order; 1 on an untextured
+// triangle and exactly 1.0f on a texture without an alpha image) at point pt (xyz) on the triangle whose rows are v0, nab = -(v1 -
 // v0), nac = -(v2 - v0) (DevTri's, or formed the same way from the quantized
 // path's vertices) and texture record V.rec[idx].  The caller bounds idx.
 // CHECK (MCPT_DEBUG builds): the texel indices are tested against the pool
@@ -103,7 +106,8 @@ __device__ inline f4 texture_factor(const TexView &V, int64_t idx, f3 v0, f3 nab
   if (t00.x == t10.x && t00.x == t01.x && t00.x == t11.x) r.x = t00.x;
   if (t00.y == t10.y && t00.y == t01.y && t00.y == t11.y) r.y = t00.y;
   if (t00.z == t10.z && t00.z == t01.z && t00.z == t11.z) r.z = t00.z;
-  r.w = 1.0f;
+  r.w = __builtin_fmaf(w11, t11.w, __builtin_fmaf(w01, t01.w, __builtin_fmaf(w10, t10.w, w00 * t00.w)));
+  if (t00.w == t10.w && t00.w == t01.w && t00.w == t11.w) r.w = t00.w;
   return r;
 }
 #endif

@@ -63,7 +63,7 @@ def reduce_image(hist, count, seeds, mask, group=None, dst=0):
 
 def render_distributed(renderer, scene, camera, width, height, max_depth, max_attempt, frames, seeds,
                        stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None, textures=None,
-                       lens=None, bump=None):
+                       lens=None, bump=None, cutouts=None):
     """Render the whole image across the process group; rank 0 gets the image.
     `jitter`: Renderer.render_frames' sub-pixel jitter (per-pixel draws, so
     still the single-GPU image for any GPU count).  `vertex_normals`: smooth
@@ -75,13 +75,16 @@ def render_distributed(renderer, scene, camera, width, height, max_depth, max_at
     on every rank (per-pixel draws like the jitter's, which it switches on: no
     bit depends on the striping).  `bump`: a (uv, tri_map, images) triple
     (scene.load_bump_maps'), set on this rank's scene like the textures
-    (Renderer.set_normal_maps).
+    (Renderer.set_normal_maps).  `cutouts`: (alphas, threshold), set on this
+    rank's scene after the textures (Renderer.set_texture_alpha).
     Returns (hist, count, seeds) as numpy on rank 0, None elsewhere."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if vertex_normals is not None:
         renderer.set_vertex_normals(scene, vertex_normals)
     if textures is not None:
         renderer.set_textures(scene, *textures)
+    if cutouts is not None:
+        renderer.set_texture_alpha(scene, *cutouts)
     if bump is not None:
         renderer.set_normal_maps(scene, *bump)
     st = renderer.new_state(width, height, seeds)

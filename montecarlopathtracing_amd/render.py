@@ -618,14 +618,42 @@ class Renderer:
             recs[k].rgb, recs[k].width, recs[k].height = L.ptr(im), im.shape[1], im.shape[0]
         tx = L.Textures(L.ptr(u), L.ptr(t), len(imgs), ctypes.cast(recs, ctypes.c_void_p))
         L.check(L.lib().mcpt_scene_set_textures(self.ctx, scene.handle, ctypes.byref(tx)))
+        scene.cutouts = None  # (a new texture set has no alpha)
 
     def clear_textures(self, scene):
         """Back to the materials' kd (the bits of a scene that never had textures)."""
         L.check(L.lib().mcpt_scene_set_textures(self.ctx, scene.handle, None))
+        scene.cutouts = None
+
+    # ------------------------------------------------ alpha cutouts (opt-in)
+    def set_texture_alpha(self, scene, alphas, threshold=0.5):
+        """mcpt_scene_set_texture_alpha: a hit on `scene` whose texture's alpha
+        is below `threshold` (in (0, 1]) is cut: the ray goes on through it.
+        alphas: one (h, w) float32 image in [0, 1], row 0 the top, of its
+        texture's size, or None (opaque), per image of set_textures
+        (scene.load_cutouts returns them).  max_depth is at most 255 on such a
+        scene.  Replaces a previous alpha and drops the primary-hit cache; a
+        later set_textures or clear_textures drops the alpha."""
+        imgs = [None if a is None else np.ascontiguousarray(a, np.float32) for a in alphas]
+        for k, a in enumerate(imgs):
+            if a is not None and a.ndim != 2:
+                raise ValueError("set_texture_alpha: alpha %d must be (height, width), got %r" % (k, a.shape))
+        ptrs = (ctypes.c_void_p * max(len(imgs), 1))()
+        for k, a in enumerate(imgs):
+            ptrs[k] = None if a is None else a.ctypes.data
+        ta = L.TextureAlpha(len(imgs), ctypes.cast(ptrs, ctypes.c_void_p), float(threshold), 0.0)
+        L.check(L.lib().mcpt_scene_set_texture_alpha(self.ctx, scene.handle, ctypes.byref(ta)))
+        scene.cutouts = float(np.float32(threshold))
+
+    def clear_texture_alpha(self, scene):
+        """Back to opaque textures (the bits of a textured scene that never had an alpha)."""
+        L.check(L.lib().mcpt_scene_set_texture_alpha(self.ctx, scene.handle, None))
+        scene.cutouts = None
 
     def texture_eval(self, scene, tri_ids, points):
         """mcpt_texture_eval: kd's factor at (triangle, hit point) queries on a
-        textured scene: a float32 (n, 4) device tensor (w = 1; zeros for an
+        textured scene: a float32 (n, 4) device tensor (w: the cutout alpha, 1
+        without one; zeros for an
         index outside the scene).  tri_ids: n int32, host or device; points:
         (n, 3) or (n, 4), host or a device (n, 4) float32 tensor."""
         if torch.is_tensor(tri_ids):
@@ -722,8 +750,40 @@ class Renderer:
     # ------------------------------------------------------ denoise (opt-in)
     def first_hits(self, scene, camera, width, height, mode=L.MODE_EXACT):
         """Every pixel's first hit (W*H Hit records, device bytes): generate_rays
-        then intersect, the corner ray's also when the render is jittered."""
-        return self.intersect(scene, self.generate_rays(camera, width, height), mode=mode)
+        then intersect, the corner ray's also when the render is jittered.  On
+        a scene with cutouts (set_texture_alpha): the first hit that is not
+        cut, its t the distance along the pixel's ray."""
+        return self._first_uncut(scene, self.generate_rays(camera, width, height), mode)
+
+    def _first_uncut(self, scene, rays, mode):
+        """intersect, and on a scene with cutouts the loop that follows the cut
+        rays on from their hit points (intersect + texture_eval on those rays
+        alone, at most 255 rounds: shading's pass-count cap)."""
+        hits = self.intersect(scene, rays, mode=mode)
+        a0 = getattr(scene, "cutouts", None)
+        if a0 is None:
+            return hits
+        h = records(hits, L.HIT).copy()
+        r = records(rays, L.RAY).copy()
+        live = np.arange(len(h))
+        t_before = np.zeros(len(h), np.float64)
+        for _ in range(255):
+            live = live[h["t"][live] < np.float32(3.0e38)]
+            if len(live) == 0:
+                break
+            alpha = self.texture_eval(scene, h["triangle_id"][live].astype(np.int32), h["point"][live]).cpu().numpy()[:, 3]
+            live = live[alpha < np.float32(a0)]
+            if len(live) == 0:
+                break
+            t_before[live] += h["t"][live].astype(np.float64)
+            sub = np.zeros(len(live), L.RAY)
+            sub["origin"][:, :3] = h["point"][live][:, :3]
+            sub["direction"] = r["direction"][live]
+            hs = records(self.intersect(scene, to_device(sub, self.device), mode=mode), L.HIT)
+            h[live] = hs
+        found = h["t"] < np.float32(3.0e38)
+        h["t"][found] = (t_before[found] + h["t"][found].astype(np.float64)).astype(np.float32)
+        return to_device(h, self.device)
 
     def autofocus(self, scene, camera, width, height, px, py, mode=L.MODE_EXACT):
         """The lens focus distance F that puts what pixel (px, py) sees in
@@ -733,7 +793,7 @@ class Renderer:
         if not (0 <= px < width and 0 <= py < height):
             raise ValueError("autofocus: pixel (%d, %d) is outside the %d x %d image" % (px, py, width, height))
         rays = self.generate_rays(camera, width, height)
-        hit = records(self.intersect(scene, rays, mode=mode), L.HIT)[py * width + px]
+        hit = records(self._first_uncut(scene, rays, mode), L.HIT)[py * width + px]
         ray = records(rays, L.RAY)[py * width + px]
         if not float(hit["t"]) < 3.0e38:
             raise ValueError("autofocus: the ray of pixel (%d, %d) hits nothing to focus on" % (px, py))

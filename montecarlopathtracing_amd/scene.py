@@ -191,17 +191,21 @@ def _srgb_table():
 SRGB_TO_LINEAR = _srgb_table()
 
 
-def decode_png(data):
+def decode_png(data, alpha=False):
     """PNG bytes -> (height, width, 3) uint8, row 0 the top.  8-bit,
     non-interlaced images of colour types 0 (grey), 2 (RGB), 3 (palette), 4
     (grey + alpha) and 6 (RGBA), all five row filters; alpha is dropped.
-    Anything else raises ValueError.  Needs zlib only."""
+    Anything else raises ValueError.  Needs zlib only.
+    alpha=True: (rgb, a) instead, a the alpha channel as (height, width)
+    float32, raw / 255 (no sRGB decode), of colour types 4 and 6 and of type 3
+    with a tRNS chunk (palette entries past its end are opaque); None for an
+    image that carries none."""
     import struct
     import zlib
     data = bytes(data)
     if data[:8] != b"\x89PNG\r\n\x1a\n":
         raise ValueError("not a PNG file")
-    pos, ihdr, plte, idat, ended = 8, None, None, [], False
+    pos, ihdr, plte, trns, idat, ended = 8, None, None, None, [], False
     while pos + 8 <= len(data) and not ended:
         n, tag = struct.unpack(">I4s", data[pos:pos + 8])
         body = data[pos + 8:pos + 8 + n]
@@ -213,6 +217,8 @@ def decode_png(data):
             ihdr = body
         elif tag == b"PLTE":
             plte = body
+        elif tag == b"tRNS":
+            trns = body
         elif tag == b"IDAT":
             idat.append(body)
         elif tag == b"IEND":
@@ -273,17 +279,26 @@ def decode_png(data):
         pal = np.frombuffer(plte, np.uint8).reshape(-1, 3)
         if int(px.max()) >= len(pal):
             raise ValueError("PNG: palette index out of range")
-        return np.ascontiguousarray(pal[px[..., 0]])
-    if ctype in (0, 4):
-        return np.ascontiguousarray(np.repeat(px[..., :1], 3, axis=2))
-    return np.ascontiguousarray(px[..., :3])
+        rgb, a = np.ascontiguousarray(pal[px[..., 0]]), None
+        if trns is not None:
+            ta = np.full(256, 255, np.uint8)
+            ta[:min(len(trns), 256)] = np.frombuffer(trns[:256], np.uint8)
+            a = ta[px[..., 0]]
+    elif ctype in (0, 4):
+        rgb, a = np.ascontiguousarray(np.repeat(px[..., :1], 3, axis=2)), (px[..., 1] if ctype == 4 else None)
+    else:
+        rgb, a = np.ascontiguousarray(px[..., :3]), (px[..., 3] if ctype == 6 else None)
+    if not alpha:
+        return rgb
+    return rgb, (None if a is None else np.ascontiguousarray(a.astype(np.float32) / np.float32(255.0)))
 
 
-def read_png(path):
-    """A PNG file as (height, width, 3) uint8, row 0 the top (decode_png)."""
+def read_png(path, alpha=False):
+    """A PNG file as (height, width, 3) uint8, row 0 the top (decode_png; with
+    alpha=True its (rgb, alpha) pair)."""
     with open(path, "rb") as fh:
         try:
-            return decode_png(fh.read())
+            return decode_png(fh.read(), alpha)
         except ValueError as e:
             raise ValueError("%s: %s" % (path, e))
 
@@ -404,6 +419,140 @@ def load_textures(directory, objname, mats, mat_index):
         print("warning: %s names texture maps but has no texture coordinates (vt): rendering untextured" % objname,
               file=sys.stderr)
     return uv, tri_tex, images
+
+
+# ------------------------------------------------- alpha cutouts (opt-in)
+def load_mtl_alpha_maps(directory, objname):
+    """Each material's map_d file name ("" without one), in load_object's
+    material order (mcpt_load_mtl_alpha_maps)."""
+    lib = L.lib()
+    nb, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+    d, o = directory.encode(), objname.encode()
+    L.check(lib.mcpt_load_mtl_alpha_maps(d, o, None, ctypes.byref(nb), ctypes.byref(nm)))
+    buf = np.zeros(max(nb.value, 1), np.uint8)
+    L.check(lib.mcpt_load_mtl_alpha_maps(d, o, L.ptr(buf), ctypes.byref(nb), ctypes.byref(nm)))
+    return _names(buf[:nb.value], nm.value)
+
+
+def mtl_alpha_maps_from_text(text):
+    """load_mtl_alpha_maps on MTL text (bytes or str) in memory."""
+    lib = L.lib()
+    t = text.encode() if isinstance(text, str) else bytes(text)
+    src = np.frombuffer(t, np.uint8) if t else np.zeros(0, np.uint8)
+    sp = L.ptr(src) if len(src) else None
+    nb, nm = ctypes.c_int64(0), ctypes.c_int64(0)
+    L.check(lib.mcpt_mtl_alpha_maps_from_text(sp, len(src), None, ctypes.byref(nb), ctypes.byref(nm)))
+    buf = np.zeros(max(nb.value, 1), np.uint8)
+    L.check(lib.mcpt_mtl_alpha_maps_from_text(sp, len(src), L.ptr(buf), ctypes.byref(nb), ctypes.byref(nm)))
+    return _names(buf[:nb.value], nm.value)
+
+
+def read_alpha(path, own_only=False):
+    """An image file's alpha as (height, width) float32 in [0, 1], row 0 the
+    top, raw (no sRGB decode): its alpha channel if it has one; else, unless
+    own_only, its first channel (8-bit: / 255); else None.  .png through
+    read_png, .hdr (no alpha channel) through read_hdr, other formats through
+    Pillow if it is importable."""
+    import os
+    if not os.path.isfile(path):
+        raise ValueError("map file %s does not exist" % path)
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".png":
+        rgb, a = read_png(path, alpha=True)
+        first = rgb[..., 0].astype(np.float32) / np.float32(255.0)
+    elif ext == ".hdr":
+        a, first = None, _read_raw_image(path)[..., 0]
+    else:
+        try:
+            from PIL import Image
+        except ImportError:
+            raise ValueError("%s: only .png (8-bit, non-interlaced) and .hdr maps are read without Pillow" % path)
+        try:
+            with Image.open(path) as im:
+                q = np.asarray(im.convert("RGBA"), np.uint8)
+                has_a = "A" in im.getbands() or "transparency" in im.info
+        except Exception as e:  # Pillow raises its own types for unknown or damaged files
+            raise ValueError("%s: %s" % (path, e))
+        a = q[..., 3].astype(np.float32) / np.float32(255.0) if has_a else None
+        first = q[..., 0].astype(np.float32) / np.float32(255.0)
+    if a is None and not own_only:
+        a = first
+    if a is None:
+        return None
+    return np.ascontiguousarray(np.clip(np.nan_to_num(a, nan=0.0, posinf=1.0, neginf=0.0), 0.0, 1.0), np.float32)
+
+
+def resample_alpha(a, height, width):
+    """An alpha image (h, w) at the texel centres of a (height, width) texture:
+    the texture lookup's repeating bilinear filter in float64, rounded once."""
+    a = np.asarray(a, np.float64)
+    h, w = a.shape
+    if (h, w) == (height, width):
+        return np.ascontiguousarray(a, np.float32)
+    x = (np.arange(width, dtype=np.float64) + 0.5) / width * w - 0.5
+    y = (np.arange(height, dtype=np.float64) + 0.5) / height * h - 0.5
+    i0, j0 = np.floor(x), np.floor(y)
+    fx, fy = (x - i0)[None, :], (y - j0)[:, None]
+    i0, j0 = i0.astype(np.int64) % w, j0.astype(np.int64) % h
+    i1, j1 = (i0 + 1) % w, (j0 + 1) % h
+    t00, t10 = a[j0][:, i0], a[j0][:, i1]
+    t01, t11 = a[j1][:, i0], a[j1][:, i1]
+    r = (1 - fx) * (1 - fy) * t00 + fx * (1 - fy) * t10 + (1 - fx) * fy * t01 + fx * fy * t11
+    return np.ascontiguousarray(np.clip(r, 0.0, 1.0), np.float32)
+
+
+def load_cutouts(directory, objname, mats, mat_index):
+    """What Renderer.set_textures and set_texture_alpha take for an OBJ model
+    with cutouts: (uv, tri_tex, images, alphas).  The first three are
+    load_textures' with, behind them, one texture of ones per map_d image of a
+    material that has a map_d but no map_Kd; alphas holds one (h, w) float32
+    image or None per texture: from the material's map_d image (its alpha
+    channel if it has one, else its first channel, raw), resampled to the
+    colour texture's size where they differ (resample_alpha); else from the
+    map_Kd image's own alpha channel.  A texture that several materials share
+    takes the first such material's map_d.  The scalars `d` and `Tr` are not
+    honoured.  Maps without `vt` give one warning line and no cutouts."""
+    import os
+    import sys
+    uv, tri_tex, images = load_textures(directory, objname, mats, mat_index)
+    images = list(images)
+    has = np.asarray(load_obj_uvs(directory, objname)[1], bool)
+    idx = np.asarray(mat_index, np.int32)
+    kd = load_mtl_maps(directory, objname)
+    md = load_mtl_alpha_maps(directory, objname)
+    n = max(len(mats), len(kd), len(md))
+    kd, md = (kd + [""] * n)[:n], (md + [""] * n)[:n]
+    alphas = [None] * len(images)
+    if any(md) and not has.any():
+        if not any(kd):  # (load_textures has warned otherwise)
+            print("warning: %s names alpha maps but has no texture coordinates (vt): rendering without cutouts" % objname,
+                  file=sys.stderr)
+        return uv, tri_tex, images, alphas
+    # load_textures' slots, rebuilt: one per distinct map_Kd path, in material order
+    slot, owner = {}, {}
+    for m in sorted(set(int(x) for x in idx[has] if 0 <= x < n and kd[x])):
+        path = os.path.join(directory, kd[m])
+        if path not in slot:
+            slot[path] = len(slot)
+        owner.setdefault(slot[path], []).append(m)
+    for t, ms in owner.items():
+        h, w = images[t].shape[:2]
+        named = [m for m in ms if md[m]]
+        if named:
+            alphas[t] = resample_alpha(read_alpha(os.path.join(directory, md[named[0]])), h, w)
+        else:
+            path = os.path.join(directory, kd[ms[0]])
+            alphas[t] = read_alpha(path, own_only=True) if os.path.splitext(path)[1].lower() != ".hdr" else None
+    extra = {}
+    for m in sorted(set(int(x) for x in idx[has] if 0 <= x < n and md[x] and not kd[x])):
+        path = os.path.join(directory, md[m])
+        if path not in extra:
+            a = read_alpha(path)
+            extra[path] = len(images)
+            images.append(np.ones(a.shape + (3,), np.float32))
+            alphas.append(a)
+        tri_tex[has & (idx == m)] = extra[path]
+    return uv, tri_tex, images, alphas
 
 
 # ------------------------------------------- bump and normal maps (opt-in)
