@@ -462,6 +462,59 @@ int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_c
                             const mcpt_render_params *params, uint32_t *seeds_dev, float *hist_dev,
                             int32_t *count_dev, void *stream);
 
+/* The estimator (opt-in, no reference counterpart; ABI 5: a new struct with
+ * new entry points).  The reference's image is not the path
+ * integral: history.cl drops every all-zero sample, so a pixel holds the mean
+ * over its NON-ZERO samples, and shade.cl's depth cap returns black for every
+ * longer path.  An estimator changes both rules; a null estimator, or {0, 0},
+ * is mcpt_render_frames_lens' call bit for bit.
+ *
+ * count_all = 1 (counted history): an all-zero sample is no longer skipped.
+ * It runs the expression of every other sample, hist = (now + hist * cnt) /
+ * (float)(cnt + 1) with the 2.5-ulp division, hist.w = 0, ++cnt; with now = 0
+ * that scales the mean by cnt / (cnt + 1).  The cnt >= max_attempt stop and the
+ * frame-index gate frame_begin + f <= max_attempt are unchanged, so count
+ * after n frames from zero is min(n, max_attempt) for every pixel of the
+ * stripes: misses, capped paths, unknown materials and black environment
+ * samples included.  The flag draws no random number: without roulette the
+ * seeds come out as the default render's.
+ *
+ * rr_depth >= 1 (Russian roulette; 0: off).  In shade, after the depth-cap
+ * test, where all of these hold: the shaded material is MCPT_DIFFUSE or
+ * MCPT_GLOSSY; a new ray was produced (not a rejected lobe sample that is drawn
+ * again, not a cut hit, not a light, not an unknown material); the cap did not
+ * end the path; the new depth (term_depth & 0xFFFF, & 0xFF on a scene with
+ * cutouts: the value the cap compares) is >= rr_depth.  Then, with R the
+ * reflectance this bounce multiplied into the colour (kd times the texture
+ * factor on the diffuse lobe, ks where the Phong lobe was taken),
+ *     p = fmin(1.0f, fmax(R.x, fmax(R.y, R.z)))
+ *     u = lcg15(seed) * 2^-15          one draw, always taken
+ *     u < p:  colour = colour / p      (the 2.5-ulp division, all four lanes)
+ *     else:   colour = 0, term_depth |= MCPT_TERMINATED, as the cap does it.
+ * p = 0 always ends the path and p = 1 never does; transparent hits and total
+ * internal reflection draw nothing.  A survivor's colour is at most what R = 1
+ * would have given it, so the rule makes no fireflies.  The survival
+ * probability is the bounce's albedo, not the path's throughput: the
+ * reference scales every bounce by 1 / 2 pi, which would make a throughput
+ * rule end nearly every path.  A path the roulette ends is a zero sample that
+ * must be counted, so rr_depth > 0 needs count_all = 1.
+ *
+ * MCPT_ERR_ARG, and nothing is touched: rr_depth > 0 with count_all = 0,
+ * rr_depth < 0 or > 65535, count_all not 0 or 1 (and what
+ * mcpt_render_frames_lens refuses).  pad is ignored.  One device function per
+ * rule runs in the fused kernel and in the wavefront kernels below
+ * (mcpt_shade_est, mcpt_accumulate_all).  The primary-hit cache is used as
+ * before: it holds hits, and shading them draws as a traced hit's does.     */
+typedef struct mcpt_estimator {
+  int32_t count_all; /* 0 | 1 */
+  int32_t rr_depth;  /* 0: off, else 1..65535 */
+  int32_t pad[2];
+} mcpt_estimator;
+int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam,
+                           const mcpt_lens *lens /* may be NULL */, const mcpt_estimator *est /* may be NULL */,
+                           const mcpt_render_params *params, uint32_t *seeds_dev, float *hist_dev,
+                           int32_t *count_dev, void *stream);
+
 /* Launch-plan knobs (speed only), kept in the context; NULL resets them.  */
 int mcpt_set_tuning(mcpt_ctx *ctx, const mcpt_tuning *tuning);
 int mcpt_get_tuning(mcpt_ctx *ctx, mcpt_tuning *out);
@@ -523,9 +576,19 @@ int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays_
 int mcpt_shade(mcpt_ctx *ctx, const mcpt_scene *scene, mcpt_ray *rays_dev,
                const mcpt_hit *hits_dev, float *color_dev, uint32_t *seeds_dev, int64_t n,
                int32_t max_depth, void *stream);
+/* mcpt_shade with mcpt_estimator's Russian roulette, on plain and textured
+ * scenes alike.  rr_depth = 0: mcpt_shade's bits; < 0 or > 65535:
+ * MCPT_ERR_ARG.                                                           */
+int mcpt_shade_est(mcpt_ctx *ctx, const mcpt_scene *scene, mcpt_ray *rays_dev,
+                   const mcpt_hit *hits_dev, float *color_dev, uint32_t *seeds_dev, int64_t n,
+                   int32_t max_depth, int32_t rr_depth, void *stream);
 /* history.cl func (-D MAX_ATTEMPT): running mean of non-zero samples      */
 int mcpt_accumulate(mcpt_ctx *ctx, float *color_dev, float *hist_dev, int32_t *count_dev,
                     int64_t n, int32_t max_attempt, void *stream);
+/* The same with mcpt_estimator's counted history: the running mean of every
+ * sample, the all-zero ones included.                                      */
+int mcpt_accumulate_all(mcpt_ctx *ctx, float *color_dev, float *hist_dev, int32_t *count_dev,
+                        int64_t n, int32_t max_attempt, void *stream);
 /* testkernel.cl func, ColorOut's display pass (colorout.cpp:58-70): per
  * pixel (pow(r, 1/2.2f), pow(g, 1/2.2f), pow(b, 1/2.2f), 0) into a float4
  * buffer (the reference writes it to its RGBA32F GL texture).  The reference

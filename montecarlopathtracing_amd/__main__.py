@@ -4,6 +4,7 @@ or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
         [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]] [--smooth [DEG]]
         [--textures] [--cutouts [THRESHOLD]] [--bump [SCALE]] [--aperture R (--focus F | --focus-at X,Y)]
+        [--unbiased] [--roulette [DEPTH]]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -54,7 +55,20 @@ def parser():
                     help="the distance along the view axis that is in focus, in scene units (with --aperture)")
     ap.add_argument("--focus-at", default=None, metavar="X,Y",
                     help="autofocus: focus on what pixel X,Y sees (with --aperture)")
+    ap.add_argument("--unbiased", action="store_true",
+                    help="count every sample in the history, the all-zero ones included: the image is the mean of "
+                         "all samples, even if the config entry has no \"unbiased\": true")
+    ap.add_argument("--roulette", nargs="?", type=int, const=True, default=None, metavar="DEPTH",
+                    help="Russian roulette on diffuse and glossy bounces from DEPTH on (default 3), the survival "
+                         "probability the bounce's albedo; switches --unbiased on, overrides the config entry's "
+                         "\"roulette\"")
     return ap
+
+
+def cli_estimator(a):
+    """The command line's (unbiased, roulette) as App takes them: None leaves
+    the entry's key; --roulette switches --unbiased on."""
+    return (True if a.unbiased or a.roulette is not None else None), a.roulette
 
 
 def cli_lens(a):
@@ -149,9 +163,11 @@ def main(argv=None):
     if ws > 1:
         return _main_dist(a)
     from .app import App
+    unbiased, roulette = cli_estimator(a)
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
               denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth,
-              textures=True if a.textures else None, lens=cli_lens(a), bump=a.bump, cutouts=a.cutouts)
+              textures=True if a.textures else None, lens=cli_lens(a), bump=a.bump, cutouts=a.cutouts,
+              unbiased=unbiased, roulette=roulette)
     if app.lens_spec is not None:
         print("lens: jitter switched on (a lens needs a fresh primary ray every frame)")
     t0 = time.time()
@@ -207,8 +223,12 @@ def _main_dist(a):
     spec = cli_lens(a)
     spec = cfg.LENS() if spec is None else C.parse_lens(spec)
     lens = resolve_lens(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, spec)  # every rank: the same lens
+    unbiased, roulette = cli_estimator(a)
+    roulette = cfg.ROULETTE() if roulette is None else C.parse_roulette(roulette)
+    unbiased = bool(unbiased or cfg.UNBIASED() or roulette)  # every rank: the same estimator
     out = D.render_distributed(rnd, sc, S.parse_camera(cfg.GETCAMERA()), w, h, cfg.MAXDEPTH(), cfg.MAXATTEPMT(),
-                               frames, R.default_seeds(w * h), jitter=a.jitter or cfg.JITTER(), lens=lens)
+                               frames, R.default_seeds(w * h), jitter=a.jitter or cfg.JITTER(), lens=lens,
+                               unbiased=unbiased, roulette=roulette)
     if dist.get_rank() == 0:
         path = os.path.join(a.out, cfg.GETOBJNAME() + ".hdr")
         S.write_hdr(path, out[0].reshape(h, w, 4), flip=True)

@@ -108,6 +108,11 @@ class Lens(ctypes.Structure):
     _fields_ = [("radius", ctypes.c_float), ("focus_distance", ctypes.c_float), ("pad", ctypes.c_float * 2)]
 
 
+class Estimator(ctypes.Structure):
+    """mcpt_estimator (16 B): count_all, rr_depth, pad[2]."""
+    _fields_ = [("count_all", ctypes.c_int32), ("rr_depth", ctypes.c_int32), ("pad", ctypes.c_int32 * 2)]
+
+
 class MCPTError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -165,6 +170,9 @@ SIGNATURES = {
     "mcpt_render_frames": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "mcpt_render_frames_lens": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcpt_generate_rays_lens": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "mcpt_render_frames_est": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcpt_shade_est": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
+    "mcpt_accumulate_all": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),
     "mcpt_generate_rays": (_I32, [_P, _P, _I32, _I32, _P, _P]),
     "mcpt_generate_rays_jittered": (_I32, [_P, _P, _I32, _I32, _P, _P, _P]),
     "mcpt_intersect": (_I32, [_P, _P, _P, _I64, _P, _F32, _I32, _P]),

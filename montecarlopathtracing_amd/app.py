@@ -62,6 +62,19 @@ instead of the reference's pinhole (Renderer.render_frames' lens).  A lens
 needs a fresh primary ray every frame, so it switches jitter on (App.jitter
 then reads True).  The denoise pass's guide stays the pinhole corner ray's
 first hit, as with jitter.
+
+Extension: "unbiased": true (App(..., unbiased=...), --unbiased) counts every
+sample in the history, the all-zero ones included, so the image is the mean of
+all samples and not of the non-zero ones (Renderer.render_frames' unbiased).
+"roulette": true | <depth >= 1> (App(..., roulette=...), --roulette [DEPTH];
+true: depth 3) ends diffuse and glossy paths from that depth on with one minus
+the bounce's albedo as the probability and divides the survivors' colour by
+it; it needs the counted history and switches it on (App.unbiased then reads
+True).  App(..., roulette=False) over an entry with a "roulette" key switches
+both off again, unless the entry's own "unbiased" key (or the argument) asks
+for the counted history.  The denoise pass runs unchanged: it weights every tap by its count,
+which is then the frame count everywhere, so a black pixel carries black at
+full weight.
 """
 import os
 
@@ -181,7 +194,7 @@ def resolve_lens(renderer, scene, camera, width, height, spec):
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
                  material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None,
-                 lens=None, bump=None, cutouts=None):
+                 lens=None, bump=None, cutouts=None, unbiased=None, roulette=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -220,6 +233,14 @@ class App:
         self.cutouts = self.cfg.CUTOUTS() if cutouts is None else C.parse_cutouts(cutouts)
         if self.cutouts is not None:
             self.textures = True
+        # None: the entry's "unbiased" / "roulette" keys; else those keys' values.  The roulette in force switches
+        # unbiased on: with roulette=False over an entry's "roulette", unbiased is what the "unbiased" key itself says.
+        self.unbiased = self.cfg.unbiased_key if unbiased is None else C.parse_unbiased(unbiased)
+        self.roulette = self.cfg.ROULETTE() if roulette is None else C.parse_roulette(roulette)
+        if self.roulette:
+            if unbiased is not None and not unbiased:
+                raise ValueError("roulette needs the counted history: unbiased=False cannot go with it")
+            self.unbiased = True
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -260,12 +281,13 @@ class App:
             # one-block trials of either would tune a regime the run never enters.
             self.renderer.tune(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, frames=16,
                                block_entries=None, last_block=False, tile_orders=None, frames_per_launch=16,
-                               jitter=self.jitter, lens=self.lens)
+                               jitter=self.jitter, lens=self.lens, unbiased=self.unbiased, roulette=self.roulette)
             self._tuned = True
         while todo > 0:
             n = todo if self.attempt_count > att else min(todo, att + 1 - self.attempt_count)
             self.renderer.render_frames(self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), att, n,
-                                        jitter=self.jitter, lens=self.lens)
+                                        jitter=self.jitter, lens=self.lens, unbiased=self.unbiased,
+                                        roulette=self.roulette)
             self.attempt_count += n
             todo -= n
             if self.attempt_count > att and self.dumped is None:

@@ -94,6 +94,29 @@ def parse_cutouts(v):
     return v
 
 
+DEFAULT_ROULETTE_DEPTH = 3  # "roulette": true
+
+
+def parse_unbiased(v):
+    """The "unbiased" extension key of a config entry -> bool."""
+    if not isinstance(v, bool):
+        raise ValueError('config "unbiased" must be true or false, got %r' % (v,))
+    return v
+
+
+def parse_roulette(v):
+    """The "roulette" extension key of a config entry -> the depth from which
+    Russian roulette runs (true: DEFAULT_ROULETTE_DEPTH), or 0 (false: none).
+    A depth is an integer in 1..65535."""
+    if isinstance(v, bool):
+        return DEFAULT_ROULETTE_DEPTH if v else 0
+    if not isinstance(v, int):
+        raise ValueError('config "roulette" must be true, false or an integer depth >= 1, got %r' % (v,))
+    if not 1 <= v <= 65535:
+        raise ValueError('config "roulette" must be a depth in 1..65535, got %r' % (v,))
+    return v
+
+
 def parse_lens(v):
     """The "lens" extension key of a config entry ->
     {"aperture": R, "focus": F or None, "focus_at": (px, py) or None}.
@@ -214,6 +237,16 @@ class Config:
         # "lens": {"aperture": R, "focus": F | "focus_at": [px, py]}: a thin-lens
         # camera (depth of field; Renderer.render_frames' lens); None: the pinhole
         self.lens = parse_lens(c["lens"]) if "lens" in c else None
+        # "unbiased": true: the history counts every sample, the all-zero ones included
+        # (Renderer.render_frames' unbiased); "roulette": true | <depth >= 1>: Russian roulette from that
+        # depth on (true: 3), which needs the counted history and switches it on
+        self.unbiased = parse_unbiased(c["unbiased"]) if "unbiased" in c else False
+        self.unbiased_key = self.unbiased  # what the "unbiased" key itself says, whatever the roulette adds
+        self.roulette = parse_roulette(c["roulette"]) if "roulette" in c else 0
+        if self.roulette:
+            if "unbiased" in c and not self.unbiased:
+                raise ValueError('config "roulette" needs the counted history: "unbiased": false cannot go with it')
+            self.unbiased = True
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -259,6 +292,8 @@ class Config:
     def ENVIRONMENT(self): return self.environment  # extension: parse_environment's dict, or None
     def SMOOTH(self): return self.smooth  # extension: smooth shading's crease angle in degrees, or None
     def LENS(self): return self.lens  # extension: parse_lens' dict (thin-lens camera), or None
+    def UNBIASED(self): return self.unbiased  # extension: the history counts every sample (on with roulette)
+    def ROULETTE(self): return self.roulette  # extension: the depth Russian roulette runs from, 0: none
     def TEXTURES(self): return self.textures  # extension: the model's map_Kd textures on the diffuse lobe
     def CUTOUTS(self): return self.cutouts  # extension: the alpha threshold of the model's cutouts (textures on), or None
     def BUMP(self): return self.bump  # extension: the height maps' slope scale of the model's bump and normal maps, or None

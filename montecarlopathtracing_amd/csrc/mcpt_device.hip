@@ -772,10 +772,18 @@ struct ShadeOut {
 // forms at the register cap keep their registers.  A cut is decided by the hit
 // alone, so a hit that is shaded again after a rejected lobe sample is not cut
 // then either.
+// rr_gate (launch-uniform): min(max_depth, rr_depth) with Russian roulette
+// (mcpt_estimator), max_depth without: the one depth compare of the hot path,
+// as before; the cap and the roulette are told apart behind it.  Where a
+// diffuse or glossy bounce made a new ray that the cap let live and whose new
+// depth (the value the cap compares) is at least rr_depth, one draw u decides:
+// with p = min(1, max(R)) of the reflectance R this bounce multiplied in (kd
+// times the texture on the diffuse lobe, ks on the Phong lobe), u < p keeps
+// the path with its colour over p, else it ends as the cap ends it.  Glass,
+// lights, cut hits, pending and bad hits draw nothing.
 template <bool G = true, class Mat = const mcpt_material, bool TX = false>
 __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, f4 color, uint32_t &seed,
-                                     int max_depth, bool &resample, f4 tex = (f4){1.0f, 1.0f, 1.0f, 1.0f},
-                                     float a0 = 0.0f) {
+                                     int max_depth, bool &resample, f4 tex, float a0, int rr_gate) {
   ShadeOut r;
   r.bad = false;
   r.new_ray = true;
@@ -803,6 +811,10 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
   auto kaks_of = [&]() { return (f4){Mp->ka_ks[0], Mp->ka_ks[1], Mp->ka_ks[2], Mp->ka_ks[3]}; };
   int32_t td = as_i(in.o.w);
   f4 no, nd;
+  // roulette: min(1, max(R)) of the reflectance R a diffuse or glossy bounce multiplies in, taken where R is in
+  // registers (one value stays live to the cap, not the material, the texture factor and the lobe); 2: no such bounce
+  float rr_p = 2.0f;
+  auto survival = [](f4 R) { return fminf(1.0f, fmaxf(R.x, fmaxf(R.y, R.z))); };
   if (!G && type == MCPT_GLOSSY) goto bad_material;  // excluded by the G = false scene check
   switch (type) {
     case MCPT_DIFFUSE:
@@ -812,7 +824,9 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
         no = in.pt + kEps * nd;
         no.w = as_f(td + 1);
         nd.w = in.d.w;
-        color = cl_div4(color * kd_of() * cl_dot3(nd.xyz, in.nrm.xyz), (float)(2 * kClPi));
+        const f4 R = kd_of();
+        rr_p = survival(R);
+        color = cl_div4(color * R * cl_dot3(nd.xyz, in.nrm.xyz), (float)(2 * kClPi));
         break;
       }
       // glossy: the lobe coin (shade.cl:115), then the Phong lobe around the
@@ -830,15 +844,15 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
       no.w = as_f(td + 1);
       nd.w = in.d.w;
       // diffuse: color * kd * cos / 2pi; glossy: color * ks * pow(cos_r, Ns) * cos / 2pi
-      f4 c;
+      const f4 R = lobe ? kaks_of() : kd_of();
+      rr_p = survival(R);
+      f4 c = color * R;
       if (lobe)
 #if MCPT_POW_LOBE
-        c = color * kaks_of() * cl_pow_lobe(cl_dot3(nd.xyz, mir.xyz), Mp->Ns);
+        c = c * cl_pow_lobe(cl_dot3(nd.xyz, mir.xyz), Mp->Ns);
 #else
-        c = color * kaks_of() * cl_pow(cl_dot3(nd.xyz, mir.xyz), Mp->Ns);
+        c = c * cl_pow(cl_dot3(nd.xyz, mir.xyz), Mp->Ns);
 #endif
-      else
-        c = color * kd_of();
       color = cl_div4(c * cl_dot3(nd.xyz, in.nrm.xyz), (float)(2 * kClPi));
       break;
     }
@@ -886,9 +900,18 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
   int32_t ntd = as_i(no.w);
   int32_t depth = ntd & 0x0000FFFF;
   if constexpr (TX) depth = ntd & (a0 > 0.0f ? 0x000000FF : 0x0000FFFF);  // cutouts: bits 8..15 count the passes
-  if (depth >= max_depth) {
-    color = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-    no.w = as_f(ntd | (int32_t)MCPT_TERMINATED);
+  if (depth >= rr_gate) {
+    if (depth >= max_depth) {
+      color = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+      no.w = as_f(ntd | (int32_t)MCPT_TERMINATED);
+    } else if (rr_p <= 1.0f) {  // roulette: survive with the albedo's probability
+      if (lcg15(seed) * 1.0f * 0x1p-15f < rr_p) {
+        color = cl_div4(color, rr_p);
+      } else {
+        color = (f4){0.0f, 0.0f, 0.0f, 0.0f};
+        no.w = as_f(ntd | (int32_t)MCPT_TERMINATED);
+      }
+    }
   }
   r.o = no;
   r.d = nd;
@@ -898,14 +921,13 @@ __device__ inline ShadeOut shade_hit(Mat *__restrict__ mats, const ShadeIn &in, 
 // the whole of shade.cl's work for one ray (the wavefront kernel)
 template <bool TX = false>
 __device__ inline ShadeOut shade_hit_full(const mcpt_material *__restrict__ mats, const ShadeIn &in, f4 color,
-                                          uint32_t &seed, int max_depth, f4 tex = (f4){1.0f, 1.0f, 1.0f, 1.0f},
-                                          float a0 = 0.0f) {
+                                          uint32_t &seed, int max_depth, f4 tex, float a0, int rr_gate) {
   bool resample = false;
   ShadeIn hit = in;
   if (TX && cutout_cut(tex.w, a0, as_i(in.o.w))) hit.mat = ~hit.mat;  // cut: shade_hit's in.mat < 0
   ShadeOut so;
   do {
-    so = shade_hit<true, const mcpt_material, TX>(mats, hit, color, seed, max_depth, resample, tex, a0);
+    so = shade_hit<true, const mcpt_material, TX>(mats, hit, color, seed, max_depth, resample, tex, a0, rr_gate);
   } while (so.pending);
   return so;
 }
@@ -914,9 +936,12 @@ __device__ inline ShadeOut shade_hit_full(const mcpt_material *__restrict__ mats
 // length(now) == 0 is evaluated as "every component is +-0": with IEEE
 // denormals the built-in's rescaling branch makes length() > 0 for any
 // non-zero (or NaN) component, so the two tests agree for every input.
-__device__ inline f4 accumulate_one(f4 now, f4 &hist, int32_t &cnt, int max_attempt) {
+// count_all (mcpt_estimator): an all-zero sample is counted like any other
+// (the mean scaled by cnt / (cnt + 1)), so the history is the mean of every
+// sample and not of the non-zero ones.
+__device__ inline f4 accumulate_one(f4 now, f4 &hist, int32_t &cnt, int max_attempt, bool count_all = false) {
   const bool zero = now.x == 0.0f && now.y == 0.0f && now.z == 0.0f && now.w == 0.0f;
-  if (zero || cnt >= max_attempt) return hist;
+  if ((zero && !count_all) || cnt >= max_attempt) return hist;
   now = cl_div4(now + hist * cnt, (float)(cnt + 1));
   hist = now;
   hist.w = 0.0f;
@@ -1034,6 +1059,7 @@ struct RenderArgs {
   float lens_radius, lens_focus;  // jittered launches: the thin lens (mcpt_lens.h), radius 0: none (last, like vnrm)
   BumpView bump;              // mapped launches: the scene's normal-map records, indexed like S.tris, and their texel pool (last, likewise)
   float cut_a0;               // textured launches: the scene's cutout threshold (shade_hit's a0), 0: no cutouts (last, likewise)
+  int32_t count_all, rr_gate;  // the estimator (mcpt_estimator): count zero samples; shade_hit's rr_gate, max_depth without roulette (last, likewise)
 };
 
 constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193, scenebuild.cpp:125)
@@ -1713,13 +1739,13 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
           ShadeOut so;
           if constexpr (TX) {
             if (A.lds_mats)
-              so = shade_hit<G, LdsMaterial, true>(lds_mat_table, in, color, seed, A.max_depth, rs, tex, A.cut_a0);
+              so = shade_hit<G, LdsMaterial, true>(lds_mat_table, in, color, seed, A.max_depth, rs, tex, A.cut_a0, A.rr_gate);
             else
-              so = shade_hit<G, const mcpt_material, true>(S.mats, in, color, seed, A.max_depth, rs, tex, A.cut_a0);
+              so = shade_hit<G, const mcpt_material, true>(S.mats, in, color, seed, A.max_depth, rs, tex, A.cut_a0, A.rr_gate);
           } else if (A.lds_mats)  // LDS-typed reads (ds_read, no flat access waiting on vector memory)
-            so = shade_hit<G>(lds_mat_table, in, color, seed, A.max_depth, rs);
+            so = shade_hit<G>(lds_mat_table, in, color, seed, A.max_depth, rs, (f4){1.0f, 1.0f, 1.0f, 1.0f}, 0.0f, A.rr_gate);
           else
-            so = shade_hit<G>(S.mats, in, color, seed, A.max_depth, rs);
+            so = shade_hit<G>(S.mats, in, color, seed, A.max_depth, rs, (f4){1.0f, 1.0f, 1.0f, 1.0f}, 0.0f, A.rr_gate);
           pending = so.pending;
           lst = pending ? kRes : kBusy;
           if (!pending) {
@@ -1733,7 +1759,7 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
         if (done) {
           // ColorOut: history runs while attemptCount <= MAX_ATTEMPT (colorout.cpp:56)
           const BlockFrames bf = block_frames(blk, A.fpl, A.nb_head, A.fpl_tail, A.frames);
-          if (A.frame_begin + bf.first + f <= A.max_attempt) (void)accumulate_one(color, hist, cnt, A.max_attempt);
+          if (A.frame_begin + bf.first + f <= A.max_attempt) (void)accumulate_one(color, hist, cnt, A.max_attempt, A.count_all != 0);
           ++f;
           fresh = f < bf.count;
           if (f == bf.count) {  // block complete: write back, fetch another next iteration
@@ -2147,7 +2173,7 @@ __global__ void __launch_bounds__(1024) k_tile_sort(const uint8_t *keys, int32_t
 template <bool TX>
 __device__ __forceinline__ void shade_one(const mcpt_material *mats, mcpt_ray *rays, const mcpt_hit *hits, f4 *colors,
                                           uint32_t *seeds, int64_t n, int max_depth, const EnvView &env, int env_on,
-                                          const DevTri *tris, int64_t n_tris, const TexView &tv, float a0) {
+                                          const DevTri *tris, int64_t n_tris, const TexView &tv, float a0, int rr_gate) {
   int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n) return;
   mcpt_ray &R = rays[id];
@@ -2176,9 +2202,9 @@ __device__ __forceinline__ void shade_one(const mcpt_material *mats, mcpt_ray *r
       const f4 v0 = T.v0, nab = T.nab, nac = T.nac;
       tex = texture_factor(tv, ti, v0.xyz, nab.xyz, nac.xyz, in.pt);
     }
-    so = shade_hit_full<true>(mats, in, colors[id], seed, max_depth, tex, a0);
+    so = shade_hit_full<true>(mats, in, colors[id], seed, max_depth, tex, a0, rr_gate);
   } else {
-    so = shade_hit_full(mats, in, colors[id], seed, max_depth);
+    so = shade_hit_full(mats, in, colors[id], seed, max_depth, (f4){1.0f, 1.0f, 1.0f, 1.0f}, 0.0f, rr_gate);
   }
   colors[id] = so.color;
   seeds[id] = seed;
@@ -2191,21 +2217,21 @@ __device__ __forceinline__ void shade_one(const mcpt_material *mats, mcpt_ray *r
   }
 }
 __global__ void k_shade(const mcpt_material *mats, mcpt_ray *rays, const mcpt_hit *hits, f4 *colors,
-                        uint32_t *seeds, int64_t n, int max_depth, EnvView env, int env_on) {
-  shade_one<false>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, nullptr, 0, TexView{}, 0.0f);
+                        uint32_t *seeds, int64_t n, int max_depth, EnvView env, int env_on, int rr_gate) {
+  shade_one<false>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, nullptr, 0, TexView{}, 0.0f, rr_gate);
 }
 __global__ void k_shade_tex(const mcpt_material *mats, mcpt_ray *rays, const mcpt_hit *hits, f4 *colors,
                             uint32_t *seeds, int64_t n, int max_depth, EnvView env, int env_on, const DevTri *tris,
-                            int64_t n_tris, TexView tv, float a0) {
-  shade_one<true>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, tris, n_tris, tv, a0);
+                            int64_t n_tris, TexView tv, float a0, int rr_gate) {
+  shade_one<true>(mats, rays, hits, colors, seeds, n, max_depth, env, env_on, tris, n_tris, tv, a0, rr_gate);
 }
 
-__global__ void k_accumulate(f4 *colors, f4 *hist, int32_t *count, int64_t n, int max_attempt) {
+__global__ void k_accumulate(f4 *colors, f4 *hist, int32_t *count, int64_t n, int max_attempt, int count_all) {
   int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (id >= n) return;
   f4 h = hist[id];
   int32_t c = count[id];
-  colors[id] = accumulate_one(colors[id], h, c, max_attempt);
+  colors[id] = accumulate_one(colors[id], h, c, max_attempt, count_all != 0);
   hist[id] = h;
   count[id] = c;
 }
@@ -3965,9 +3991,28 @@ int mcpt_render_frames(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera
 
 int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_lens *lens,
                             const mcpt_render_params *p, uint32_t *seeds, float *hist, int32_t *count, void *stream) {
+  return mcpt_render_frames_est(ctx, scene, cam, lens, nullptr, p, seeds, hist, count, stream);
+}
+
+// An estimator argument's values (null: the default estimator): 0 fine, else MCPT_ERR_ARG.
+static int check_estimator(const mcpt_estimator *est) {
+  if (!est) return MCPT_OK;
+  if (est->count_all != 0 && est->count_all != 1)
+    return mcpt::fail(MCPT_ERR_ARG, "render: bad estimator (count_all is 0 or 1)");
+  if (est->rr_depth < 0 || est->rr_depth > 65535)
+    return mcpt::fail(MCPT_ERR_ARG, "render: bad estimator (rr_depth is 0, off, or 1..65535)");
+  if (est->rr_depth > 0 && !est->count_all)
+    return mcpt::fail(MCPT_ERR_ARG, "render: Russian roulette (rr_depth > 0) needs count_all = 1");
+  return MCPT_OK;
+}
+
+int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_lens *lens,
+                           const mcpt_estimator *est, const mcpt_render_params *p, uint32_t *seeds, float *hist,
+                           int32_t *count, void *stream) {
   if (!ctx || !scene || !cam || !p || !seeds || !hist || !count) return mcpt::fail(MCPT_ERR_ARG, "render: null argument");
   MCPT_TRY(check_render(p));
   MCPT_TRY(check_lens(lens, "render"));
+  MCPT_TRY(check_estimator(est));
   const bool lens_on = lens && lens->radius > 0.0f;
   if (lens_on && p->jitter != 1) return mcpt::fail(MCPT_ERR_ARG, "render: a lens needs params->jitter = 1");
   if (scene->cut_a0 > 0.0f && p->max_depth > 255)
@@ -3982,6 +4027,8 @@ int mcpt_render_frames_lens(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_c
   A.tex = TexView{scene->texrec, scene->texels, scene->n_texels};
   A.bump = BumpView{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
   A.cut_a0 = scene->cut_a0;
+  A.count_all = est ? est->count_all : 0;
+  A.rr_gate = est && est->rr_depth > 0 ? std::min(est->rr_depth, p->max_depth) : p->max_depth;
   A.lens_radius = lens_on ? lens->radius : 0.0f, A.lens_focus = lens_on ? lens->focus_distance : 1.0f;
   A.seeds = seeds;
   A.hist = (f4 *)hist;
@@ -4125,8 +4172,15 @@ int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays,
 
 int mcpt_shade(mcpt_ctx *ctx, const mcpt_scene *scene, mcpt_ray *rays, const mcpt_hit *hits, float *color,
                uint32_t *seeds, int64_t n, int32_t max_depth, void *stream) {
+  return mcpt_shade_est(ctx, scene, rays, hits, color, seeds, n, max_depth, 0, stream);
+}
+
+int mcpt_shade_est(mcpt_ctx *ctx, const mcpt_scene *scene, mcpt_ray *rays, const mcpt_hit *hits, float *color,
+                   uint32_t *seeds, int64_t n, int32_t max_depth, int32_t rr_depth, void *stream) {
   if (!ctx || !scene || !rays || !hits || !color || !seeds || n < 0 || max_depth <= 0)
     return mcpt::fail(MCPT_ERR_ARG, "shade: bad argument");
+  if (rr_depth < 0 || rr_depth > 65535) return mcpt::fail(MCPT_ERR_ARG, "shade: bad rr_depth (0, off, or 1..65535)");
+  const int rr = rr_depth > 0 ? std::min(rr_depth, max_depth) : max_depth;  // shade_hit's rr_gate
   if (scene->cut_a0 > 0.0f && max_depth > 255)
     return mcpt::fail(MCPT_ERR_ARG, "shade: max_depth above 255 on a scene with cutouts");
   if (n == 0) return MCPT_OK;
@@ -4134,23 +4188,33 @@ int mcpt_shade(mcpt_ctx *ctx, const mcpt_scene *scene, mcpt_ray *rays, const mcp
   if (scene->texrec)
     hipLaunchKernelGGL(k_shade_tex, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene->mats,
                        rays, hits, (f4 *)color, seeds, n, max_depth, scene->env, scene->env_on ? 1 : 0, scene->tris,
-                       scene->n_tris, TexView{scene->texrec, scene->texels, scene->n_texels}, scene->cut_a0);
+                       scene->n_tris, TexView{scene->texrec, scene->texels, scene->n_texels}, scene->cut_a0, rr);
   else
     hipLaunchKernelGGL(k_shade, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scene->mats, rays,
-                       hits, (f4 *)color, seeds, n, max_depth, scene->env, scene->env_on ? 1 : 0);
+                       hits, (f4 *)color, seeds, n, max_depth, scene->env, scene->env_on ? 1 : 0, rr);
+  HIP_OK(hipGetLastError());
+  return MCPT_OK;
+}
+
+static int accumulate(mcpt_ctx *ctx, float *color, float *hist, int32_t *count, int64_t n, int32_t max_attempt,
+                      int count_all, void *stream) {
+  if (!ctx || !color || !hist || !count || n < 0) return mcpt::fail(MCPT_ERR_ARG, "accumulate: bad argument");
+  if (n == 0) return MCPT_OK;
+  HIP_OK(hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (f4 *)color,
+                     (f4 *)hist, count, n, max_attempt, count_all);
   HIP_OK(hipGetLastError());
   return MCPT_OK;
 }
 
 int mcpt_accumulate(mcpt_ctx *ctx, float *color, float *hist, int32_t *count, int64_t n, int32_t max_attempt,
                     void *stream) {
-  if (!ctx || !color || !hist || !count || n < 0) return mcpt::fail(MCPT_ERR_ARG, "accumulate: bad argument");
-  if (n == 0) return MCPT_OK;
-  HIP_OK(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_accumulate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (f4 *)color,
-                     (f4 *)hist, count, n, max_attempt);
-  HIP_OK(hipGetLastError());
-  return MCPT_OK;
+  return accumulate(ctx, color, hist, count, n, max_attempt, 0, stream);
+}
+
+int mcpt_accumulate_all(mcpt_ctx *ctx, float *color, float *hist, int32_t *count, int64_t n, int32_t max_attempt,
+                        void *stream) {
+  return accumulate(ctx, color, hist, count, n, max_attempt, 1, stream);
 }
 
 int mcpt_gamma_preview(mcpt_ctx *ctx, const float *color, float *out, int64_t n, void *stream) {

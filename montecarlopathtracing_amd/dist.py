@@ -63,7 +63,7 @@ def reduce_image(hist, count, seeds, mask, group=None, dst=0):
 
 def render_distributed(renderer, scene, camera, width, height, max_depth, max_attempt, frames, seeds,
                        stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None, textures=None,
-                       lens=None, bump=None, cutouts=None):
+                       lens=None, bump=None, cutouts=None, unbiased=False, roulette=0):
     """Render the whole image across the process group; rank 0 gets the image.
     `jitter`: Renderer.render_frames' sub-pixel jitter (per-pixel draws, so
     still the single-GPU image for any GPU count).  `vertex_normals`: smooth
@@ -76,7 +76,9 @@ def render_distributed(renderer, scene, camera, width, height, max_depth, max_at
     bit depends on the striping).  `bump`: a (uv, tri_map, images) triple
     (scene.load_bump_maps'), set on this rank's scene like the textures
     (Renderer.set_normal_maps).  `cutouts`: (alphas, threshold), set on this
-    rank's scene after the textures (Renderer.set_texture_alpha).
+    rank's scene after the textures (Renderer.set_texture_alpha).  `unbiased`,
+    `roulette`: Renderer.render_frames' estimator on every rank (each pixel
+    belongs to one rank and draws from its own chain, so striping changes no bit).
     Returns (hist, count, seeds) as numpy on rank 0, None elsewhere."""
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if vertex_normals is not None:
@@ -89,7 +91,7 @@ def render_distributed(renderer, scene, camera, width, height, max_depth, max_at
         renderer.set_normal_maps(scene, *bump)
     st = renderer.new_state(width, height, seeds)
     kw = dict(stripe_rows=stripe_rows, stripe_index=rank, stripe_count=world, mode=mode,
-              jitter=True if lens is not None else jitter, lens=lens)
+              jitter=True if lens is not None else jitter, lens=lens, unbiased=unbiased, roulette=roulette)
     if frames >= 4096:  # long runs: each rank times the leaf schedules and S/fetch thresholds on one-block
         # 16-frame calls (same bits; neither block sizing nor tile order is tuned: long calls run
         # max_block_frames blocks, a regime one-block trials do not enter, App.update)

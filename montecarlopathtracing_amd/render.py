@@ -50,6 +50,30 @@ def _lens_struct(lens):
         raise ValueError("lens must be (radius, focus_distance), got %r" % (lens,))
 
 
+def _roulette_depth(roulette):
+    """render_frames' `roulette` -> mcpt_estimator.rr_depth: False / 0 off,
+    True depth 3, else the depth (its range is checked by the library)."""
+    if roulette is True:
+        return 3
+    if roulette is False or roulette is None:
+        return 0
+    if isinstance(roulette, (int, np.integer)):
+        return int(roulette)
+    raise ValueError("roulette must be a depth (an integer, 0: off) or a bool, got %r" % (roulette,))
+
+
+def _estimator_struct(unbiased, roulette):
+    """(unbiased, roulette) -> L.Estimator, or None for the default estimator.
+    Roulette without the counted history is refused here, before any C call."""
+    depth = _roulette_depth(roulette)
+    if depth > 0 and not unbiased:
+        raise ValueError("render_frames: roulette needs unbiased=True (a path it ends is a zero sample "
+                         "that has to be counted)")
+    if not unbiased and depth == 0:
+        return None
+    return L.Estimator(int(bool(unbiased)), depth)
+
+
 def focus_from_hit(t, ray_direction, camera_direction):
     """The focus distance that puts a first hit in focus: F = t * dot(d, c^),
     the hit's distance `t` along the unit ray direction `d`, measured along the
@@ -288,7 +312,7 @@ class Renderer:
     # ---------------------------------------------------------- fused path
     def render_frames(self, scene, camera, state, max_depth, max_attempt, frames, frame_begin=None,
                       stripe_rows=16, stripe_index=0, stripe_count=1, mode=L.MODE_EXACT,
-                      frames_per_launch=0, schedule=None, jitter=None, lens=None):
+                      frames_per_launch=0, schedule=None, jitter=None, lens=None, unbiased=False, roulette=0):
         """Frames [frame_begin, frame_begin+frames) for this GPU's row stripes
         (OpenCL::update x frames + ColorOut accumulation).  `schedule`
         (L.SCHED_*; default: the scene's, see tune_schedule) only changes speed.
@@ -301,7 +325,15 @@ class Renderer:
         thin lens of radius R focused at distance F along the view axis, in
         scene units.  A lens needs a fresh primary ray every frame, so it
         switches `jitter` on; jitter=False given with a lens is a ValueError.
-        R = 0 is no lens (the jittered call's bits)."""
+        R = 0 is no lens (the jittered call's bits).
+        `unbiased` (opt-in; mcpt_estimator.count_all): the history counts every
+        sample, the all-zero ones included, so a pixel is the mean of all its
+        samples and `count` the frame count.  `roulette` (mcpt_estimator.rr_depth;
+        0: off): Russian roulette on diffuse and glossy bounces from that depth
+        on, the survival probability the bounce's albedo.  A path it ends is a
+        zero sample that has to be counted: roulette > 0 with unbiased=False is
+        a ValueError."""
+        est_c = _estimator_struct(unbiased, roulette)
         lens_c = _lens_struct(lens)
         if lens_c is not None:
             if jitter is not None and not jitter:
@@ -320,7 +352,12 @@ class Renderer:
         p.schedule = int(getattr(scene, "schedule", L.SCHED_PAIRED) if schedule is None else schedule)
         p.jitter = int(jitter)
         cam = np.ascontiguousarray(camera)
-        if lens_c is not None:
+        if est_c is not None:
+            L.check(L.lib().mcpt_render_frames_est(self.ctx, scene.handle, L.ptr(cam),
+                                                   None if lens_c is None else ctypes.byref(lens_c),
+                                                   ctypes.byref(est_c), ctypes.byref(p), L.ptr(state.seeds),
+                                                   L.ptr(state.hist), L.ptr(state.count), _stream()))
+        elif lens_c is not None:
             L.check(L.lib().mcpt_render_frames_lens(self.ctx, scene.handle, L.ptr(cam), ctypes.byref(lens_c),
                                                     ctypes.byref(p), L.ptr(state.seeds), L.ptr(state.hist),
                                                     L.ptr(state.count), _stream()))
@@ -335,7 +372,7 @@ class Renderer:
         `frames` frames `trials` times with each schedule on a scratch copy
         of `state` (interleaved, device time of each call), keep the faster
         in scene.schedule.  Both schedules give bit-identical images, so this
-        only moves speed.  Keywords (`jitter` and `lens` among them) go to the scratch
+        only moves speed.  Keywords (`jitter`, `lens`, `unbiased` and `roulette` among them) go to the scratch
         renders it times.  Returns (schedule, {schedule: best ms})."""
         sched, _, best = self.tune(scene, camera, state, max_depth, max_attempt, frames, trials, shade_thresholds=None,
                                    fetch_thresholds=None, tile_orders=None, **kw)
@@ -361,7 +398,7 @@ class Renderer:
         predict; the minimum favoured lucky runs).  fresh_view: every trial
         call first drops the primary-hit cache, so it pays the primary-hit
         pass and the tile sort as a call of a new view does (bench.py's timed
-        call).  Keywords of render_frames (mode, stripes, `jitter`, `lens`) go to every
+        call).  Keywords of render_frames (mode, stripes, `jitter`, `lens`, `unbiased`, `roulette`) go to every
         scratch render, so a jittered or defocused render is tuned as it will run.  The winner goes to
         scene.schedule and the renderer's tuning.  Returns (schedule,
         shade_threshold, {(schedule, shade, fetch, entries, tile_order): median ms})."""
@@ -495,17 +532,23 @@ class Renderer:
                                        _stream()))
         return hits
 
-    def shade(self, scene, rays, hits, color, seeds, max_depth):
-        """shade.cl on (rays, hits, colour, seeds) in place."""
+    def shade(self, scene, rays, hits, color, seeds, max_depth, roulette=0):
+        """shade.cl on (rays, hits, colour, seeds) in place.  `roulette` > 0:
+        with render_frames' Russian roulette from that depth (mcpt_shade_est)."""
         n = rays.numel() // L.RAY.itemsize
+        if roulette:
+            L.check(L.lib().mcpt_shade_est(self.ctx, scene.handle, L.ptr(rays), L.ptr(hits), L.ptr(color), L.ptr(seeds),
+                                           n, int(max_depth), _roulette_depth(roulette), _stream()))
+            return
         L.check(L.lib().mcpt_shade(self.ctx, scene.handle, L.ptr(rays), L.ptr(hits), L.ptr(color), L.ptr(seeds), n,
                                    int(max_depth), _stream()))
 
-    def accumulate(self, color, hist, count, max_attempt):
-        """history.cl: running mean of non-zero samples."""
+    def accumulate(self, color, hist, count, max_attempt, count_all=False):
+        """history.cl: running mean of non-zero samples; count_all: of every
+        sample (render_frames' `unbiased`; mcpt_accumulate_all)."""
         n = count.numel()
-        L.check(L.lib().mcpt_accumulate(self.ctx, L.ptr(color), L.ptr(hist), L.ptr(count), n, int(max_attempt),
-                                        _stream()))
+        fn = L.lib().mcpt_accumulate_all if count_all else L.lib().mcpt_accumulate
+        L.check(fn(self.ctx, L.ptr(color), L.ptr(hist), L.ptr(count), n, int(max_attempt), _stream()))
 
     def gamma_preview(self, color, out=None):
         """testkernel.cl func (ColorOut's GL display pass): float4 colours ->
