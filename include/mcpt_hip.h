@@ -515,6 +515,81 @@ int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ca
                            const mcpt_render_params *params, uint32_t *seeds_dev, float *hist_dev,
                            int32_t *count_dev, void *stream);
 
+/* Tile-subset render (opt-in, no reference counterpart; ABI 5: a new struct
+ * with new entry points).  k_render hands out work by 8x8
+ * tile; a tile set names the tiles a call renders.  Tiles are the image's,
+ * row-major over ceil(W/8) x ceil(H/8); an edge tile's pixels outside the image
+ * do not exist.
+ *
+ * mcpt_render_frames_tiles is mcpt_render_frames_est with a tile set.
+ *  - tiles == NULL: mcpt_render_frames_est's call bit for bit (that entry point
+ *    is this one with NULL).  A mask without a zero byte: the same.
+ *  - a mask of zero bytes only: MCPT_OK; no launch is enqueued, no state is
+ *    touched, and mcpt_stats.launches of the call is 0.
+ *  - otherwise every pixel of a tile whose byte is nonzero is advanced exactly
+ *    as the whole-image call advances it: seeds, hist and count come out with
+ *    the whole-image call's bits (a pixel draws from its own seed chain alone).
+ *    The seeds, hist and count words of every other pixel are neither read nor
+ *    written; with stats on, mcpt_stats and mcpt_set_pixel_segments count the
+ *    active pixels' work alone.
+ * MCPT_ERR_ARG, and nothing is touched: mask == NULL in a non-null set,
+ * n_tiles != ceil(W/8) * ceil(H/8), params->stripe_count != 1 (tile ids are
+ * plain image tiles; a striped subset is not defined), and everything
+ * mcpt_render_frames_est refuses.  pad is ignored.
+ * mask is host memory, read before the call returns and not kept.  The
+ * library derives the list of active tiles itself (in range and distinct by
+ * construction: two entries for one pixel would put two lanes on its hand-off
+ * chain), in a context-owned device buffer written on `stream` behind the
+ * work already enqueued there; like the context's other launch buffers it
+ * serves the calls of one stream at a time.  The list's order is speed only:
+ * the view's dearest-first tile order filtered by the mask where the call has
+ * one, else ascending.  The primary-hit cache stays whole-view: a subset call
+ * reads it by pixel id and, where a whole-image call would build it, builds
+ * it for every tile; a jittered or lens call does without it as always.     */
+typedef struct mcpt_tile_set {
+  const uint8_t *mask; /* host; one byte per 8x8 tile, row-major; nonzero = render */
+  int32_t n_tiles;     /* ceil(W/8) * ceil(H/8) */
+  int32_t pad;
+} mcpt_tile_set;
+int mcpt_render_frames_tiles(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam,
+                             const mcpt_lens *lens /* may be NULL */, const mcpt_estimator *est /* may be NULL */,
+                             const mcpt_tile_set *tiles /* may be NULL */, const mcpt_render_params *params,
+                             uint32_t *seeds_dev, float *hist_dev, int32_t *count_dev, void *stream);
+
+/* Half-buffer noise estimate (opt-in, no reference counterpart; Dammertz et
+ * al. 2010).  A render's frames go alternately into two
+ * histories A and B (hist + count each, as the render calls keep them); their
+ * difference relative to the brightness estimates the error of their mean.
+ * Both calls read their inputs only, are ordered on `stream`, asynchronous,
+ * and give the same bits for the same inputs.  fp32 throughout; a / b below is
+ * the device's 2.5-ulp division, sqrt its square root (1 ulp), fma one rounding.
+ *
+ * Merged mean of a pixel, per channel c of x, y, z, with fA = (float)nA,
+ * fB = (float)nB:   nB == 0: A's four words, bit for bit;  nA == 0: B's;
+ *   both 0: four zero words (the first rule);  else
+ *   m.c = fma(fA, A.c, fB * B.c) / (float)(nA + nB),   m.w = 0.
+ * Merged count nA + nB.  mcpt_merge_halves writes both for n pixels.
+ *
+ * Pixel error, with m as above:
+ *   d = (|A.x - B.x| + |A.y - B.y|) + |A.z - B.z|
+ *   s = fmax(((floor + m.x) + m.y) + m.z, floor)     (the fmax never acts on means >= 0)
+ *   e = (0.5f * d) / sqrt(s),      e = +inf where nA == 0 or nB == 0.
+ * Tile error (mcpt_tile_error, one float per 8x8 tile, row-major as above):
+ * the tile's pixels outside the image count 0; the 64 values are summed by the
+ * butterfly v[k] += v[k ^ 32], then ^ 16, 8, 4, 2, 1 (k = row * 8 + column in
+ * the tile), and the sum is divided by (float)(pixels inside the image).
+ * Every term is non-negative, so the result is within 28 * 2^-24 relative of
+ * the real-arithmetic value (DESIGN.md 3.19 adds it up); an inf or NaN input
+ * carries through.
+ * MCPT_ERR_ARG: a null pointer, width or height <= 0 (n < 0), floor not
+ * finite or <= 0, a hist pointer not 16-byte aligned.  n == 0 does nothing.  */
+int mcpt_tile_error(mcpt_ctx *ctx, int32_t width, int32_t height, const float *histA_dev, const int32_t *countA_dev,
+                    const float *histB_dev, const int32_t *countB_dev, float floor, float *err_dev /* n_tiles */,
+                    void *stream);
+int mcpt_merge_halves(mcpt_ctx *ctx, const float *histA_dev, const int32_t *countA_dev, const float *histB_dev,
+                      const int32_t *countB_dev, int64_t n, float *hist_out_dev, int32_t *count_out_dev,
+                      void *stream);
+
 /* Launch-plan knobs (speed only), kept in the context; NULL resets them.  */
 int mcpt_set_tuning(mcpt_ctx *ctx, const mcpt_tuning *tuning);
 int mcpt_get_tuning(mcpt_ctx *ctx, mcpt_tuning *out);

@@ -4,7 +4,7 @@ or, for a "testbvh" / "testall" entry, print the BVH metrics (main.cpp:11-25).
     python -m montecarlopathtracing_amd [config.json] [--configid N] [--out DIR] [--preview PNG] [--jitter] [--denoise]
         [--env R,G,B | --env-map FILE [--env-scale S|R,G,B] [--env-rotate DEG]] [--smooth [DEG]]
         [--textures] [--cutouts [THRESHOLD]] [--bump [SCALE]] [--aperture R (--focus F | --focus-at X,Y)]
-        [--unbiased] [--roulette [DEPTH]]
+        [--unbiased] [--roulette [DEPTH]] [--adaptive [THRESHOLD]] [--adaptive-map]
     torchrun --nproc-per-node 8 -m montecarlopathtracing_amd config.json   (row-stripe tiles)
 """
 import argparse
@@ -62,6 +62,13 @@ def parser():
                     help="Russian roulette on diffuse and glossy bounces from DEPTH on (default 3), the survival "
                          "probability the bounce's albedo; switches --unbiased on, overrides the config entry's "
                          "\"roulette\"")
+    ap.add_argument("--adaptive", nargs="?", type=float, const=True, default=None, metavar="THRESHOLD",
+                    help="adaptive sampling: after the first frames only the 8x8 tiles whose half-buffer error "
+                         "estimate is above THRESHOLD (default 0.02) go on, up to attempt+1 frames; switches "
+                         "--unbiased on, overrides the config entry's \"adaptive\" threshold (one GPU only)")
+    ap.add_argument("--adaptive-map", action="store_true",
+                    help="with adaptive sampling also write <objname>_samples.hdr: each pixel's sample count over "
+                         "the budget, as grey")
     return ap
 
 
@@ -69,6 +76,18 @@ def cli_estimator(a):
     """The command line's (unbiased, roulette) as App takes them: None leaves
     the entry's key; --roulette switches --unbiased on."""
     return (True if a.unbiased or a.roulette is not None else None), a.roulette
+
+
+def cli_adaptive(a, cfg):
+    """The command line's (adaptive, adaptive_map) as App takes them: None leaves the entry's key.
+    --adaptive alone is the default threshold; --adaptive T over an entry with an "adaptive" object
+    replaces its threshold and keeps the rest."""
+    from . import config as C
+    spec = None
+    if a.adaptive is not None:
+        spec = dict(cfg.ADAPTIVE() or {})
+        spec["threshold"] = C.DEFAULT_ADAPTIVE_THRESHOLD if a.adaptive is True else a.adaptive
+    return spec, (True if a.adaptive_map else None)
 
 
 def cli_lens(a):
@@ -164,13 +183,18 @@ def main(argv=None):
         return _main_dist(a)
     from .app import App
     unbiased, roulette = cli_estimator(a)
+    adaptive, adaptive_map = cli_adaptive(a, cfg)
+    if adaptive is not None:
+        unbiased = True
     app = App(a.config, a.configid, out_dir=a.out, jitter=True if a.jitter else None,
               denoise=True if a.denoise else None, environment=cli_environment(a, cfg), smooth=a.smooth,
               textures=True if a.textures else None, lens=cli_lens(a), bump=a.bump, cutouts=a.cutouts,
-              unbiased=unbiased, roulette=roulette)
+              unbiased=unbiased, roulette=roulette, adaptive=adaptive, adaptive_map=adaptive_map)
     if app.lens_spec is not None:
         print("lens: jitter switched on (a lens needs a fresh primary ray every frame)")
     t0 = time.time()
+    if a.frames and app.adaptive is not None:
+        raise ValueError("--frames does not go with adaptive sampling: its budget is the entry's attempt + 1")
     if a.frames:
         app.update(a.frames)
         path = app.output_picture()
@@ -192,6 +216,8 @@ def _main_dist(a):
     from . import render as R
     from . import scene as S
     from .app import apply_bump, apply_environment, apply_smooth, apply_textures, config_scene, resolve_lens
+    # adaptive sampling is single-GPU: refused here, before any rank touches a GPU
+    D.refuse_adaptive(a.adaptive is not None or a.adaptive_map or C.Config(a.config, a.configid).ADAPTIVE() is not None)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # MCPT_DIST_SHARED_GPU=1 rehearses the N-rank job on a one-GPU box: every
     # rank on device 0, gloo for the one reduce (tests/test_gpu_dist.py)

@@ -113,6 +113,11 @@ class Estimator(ctypes.Structure):
     _fields_ = [("count_all", ctypes.c_int32), ("rr_depth", ctypes.c_int32), ("pad", ctypes.c_int32 * 2)]
 
 
+class TileSet(ctypes.Structure):
+    """mcpt_tile_set (16 B): mask (host uint8, one byte per 8x8 tile), n_tiles, pad."""
+    _fields_ = [("mask", ctypes.c_void_p), ("n_tiles", ctypes.c_int32), ("pad", ctypes.c_int32)]
+
+
 class MCPTError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -171,6 +176,9 @@ SIGNATURES = {
     "mcpt_render_frames_lens": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mcpt_generate_rays_lens": (_I32, [_P, _P, _P, _I32, _I32, _P, _P, _P]),
     "mcpt_render_frames_est": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcpt_render_frames_tiles": (_I32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mcpt_tile_error": (_I32, [_P, _I32, _I32, _P, _P, _P, _P, _F32, _P, _P]),
+    "mcpt_merge_halves": (_I32, [_P, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "mcpt_shade_est": (_I32, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "mcpt_accumulate_all": (_I32, [_P, _P, _P, _P, _I64, _I32, _P]),
     "mcpt_generate_rays": (_I32, [_P, _P, _I32, _I32, _P, _P]),

@@ -75,6 +75,19 @@ both off again, unless the entry's own "unbiased" key (or the argument) asks
 for the counted history.  The denoise pass runs unchanged: it weights every tap by its count,
 which is then the frame count everywhere, so a black pixel carries black at
 full weight.
+
+Extension: "adaptive": <threshold> or {"threshold": t, "min_frames": n,
+"batch": b, "floor": f, "dilate": bool, "map": bool} (App(..., adaptive=...),
+--adaptive [THRESHOLD], --adaptive-map) spends the frames where the image is
+noisy (Renderer.render_adaptive): after min_frames frames everywhere, only the
+8x8 tiles whose half-buffer error estimate is above the threshold (and their
+neighbours) go on, in batches, up to the budget of attempt + 1 frames rounded
+down to even (min_frames is cut to the budget).  It runs on the counted history
+and switches it on (App.unbiased then reads True).  update() runs the whole
+render once, whatever its frame argument, and dumps <objname>.hdr; with "map"
+also <objname>_samples.hdr, each pixel's count over the budget as grey.  The
+denoise pass runs unchanged: it weights every tap by its count, which now
+differs by tile.
 """
 import os
 
@@ -194,7 +207,8 @@ def resolve_lens(renderer, scene, camera, width, height, spec):
 class App:
     def __init__(self, cfg, configid=None, device=0, seeds=None, out_dir=".", root=None,
                  material_override=None, jitter=None, denoise=None, environment=None, smooth=None, textures=None,
-                 lens=None, bump=None, cutouts=None, unbiased=None, roulette=None):
+                 lens=None, bump=None, cutouts=None, unbiased=None, roulette=None, adaptive=None,
+                 adaptive_map=None):
         self.cfg = cfg if isinstance(cfg, C.Config) else C.Config(cfg, configid)
         if self.cfg.TESTBVH() or self.cfg.TESTALL():
             raise ValueError("testbvh/testall modes are BVH-quality tools, not the render path")
@@ -241,6 +255,22 @@ class App:
             if unbiased is not None and not unbiased:
                 raise ValueError("roulette needs the counted history: unbiased=False cannot go with it")
             self.unbiased = True
+        # None: the entry's "adaptive" key; False: off; else that key's value (a threshold or an object).
+        # Adaptive sampling runs on the counted history and switches it on.
+        if adaptive is None:
+            self.adaptive = self.cfg.ADAPTIVE()
+        else:
+            self.adaptive = None if adaptive is False else C.parse_adaptive(adaptive)
+        if self.adaptive is not None:
+            self.adaptive = dict(self.adaptive)
+            if adaptive_map is not None:
+                self.adaptive["map"] = bool(adaptive_map)
+            if unbiased is not None and not unbiased:
+                raise ValueError("adaptive sampling needs the counted history: unbiased=False cannot go with it")
+            self.unbiased = True
+        elif adaptive_map:
+            raise ValueError("adaptive_map needs adaptive sampling")
+        self.adaptive_report = None  # Renderer.render_adaptive's report once update() has run it
         self.attempt_count = 0
         self.dumped = None
         self._init = False
@@ -273,6 +303,10 @@ class App:
         if not self._init:
             self.init()
         att = self.cfg.MAXATTEPMT()
+        if self.adaptive is not None:
+            if self.adaptive_report is None:
+                self._update_adaptive(att)
+            return self.state
         todo = frames
         if frames >= 4096 and not getattr(self, "_tuned", False):  # long runs: time the leaf schedules, S-phase
             # and fetch thresholds on one-block 16-frame calls (7 trials, 112 scratch frames, bit-identical
@@ -294,6 +328,31 @@ class App:
                 self.dumped = self.output_picture()
         return self.state
 
+    def adaptive_budget(self):
+        """The per-pixel frame budget of an adaptive render: attempt + 1, rounded down to even."""
+        return (self.cfg.MAXATTEPMT() + 1) // 2 * 2
+
+    def _update_adaptive(self, att):
+        a, budget = self.adaptive, self.adaptive_budget()
+        self.adaptive_report = self.renderer.render_adaptive(
+            self.scene, self.camera, self.state, self.cfg.MAXDEPTH(), budget, a["threshold"],
+            min_frames=min(a["min_frames"], budget), batch=a["batch"], floor=a["floor"], dilate=a["dilate"],
+            jitter=self.jitter, lens=self.lens, roulette=self.roulette)
+        self.attempt_count = att + 1
+        self.dumped = self.output_picture()
+
+    def samples_image(self):
+        """An adaptive render's sample map: each pixel's count over the budget as grey, H x W x 4 floats (w = 0)."""
+        g = self.state.count.cpu().numpy().astype(np.float32) / np.float32(self.adaptive_budget())
+        out = np.zeros((self.h, self.w, 4), np.float32)
+        out[..., :3] = g.reshape(self.h, self.w, 1)
+        return out
+
+    @staticmethod
+    def samples_path(path):
+        """<name>.hdr -> <name>_samples.hdr."""
+        return (path[:-4] if path.endswith(".hdr") else path) + "_samples.hdr"
+
     def output_picture(self, path=None):
         """ThirdPartyWrapper::outputPicture(<objname>.hdr, frameBuffer); with
         denoise on also <objname>_denoised.hdr beside it (denoised_path)."""
@@ -301,6 +360,8 @@ class App:
         S.write_hdr(path, self.state.image(), flip=True)
         if self.denoise:
             S.write_hdr(self.denoised_path(path), self.denoised(), flip=True)
+        if self.adaptive is not None and self.adaptive["map"]:
+            S.write_hdr(self.samples_path(path), self.samples_image(), flip=True)
         return path
 
     @staticmethod

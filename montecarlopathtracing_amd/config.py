@@ -117,6 +117,56 @@ def parse_roulette(v):
     return v
 
 
+DEFAULT_ADAPTIVE_THRESHOLD = 0.02  # --adaptive without a value.  A starting point, not a tuned optimum
+
+
+def parse_adaptive(v):
+    """The "adaptive" extension key of a config entry ->
+    {"threshold": t, "min_frames": n, "batch": b, "floor": f, "dilate": bool, "map": bool}
+    (Renderer.render_adaptive's arguments; "map": also write the sample map).
+    A number is the threshold alone; an object names any of the six, and needs
+    "threshold".  ValueError on strings and other types, unknown keys,
+    non-positive or non-finite numbers, and counts that are not even integers
+    >= 2."""
+    out = {"threshold": None, "min_frames": 16, "batch": 8, "floor": 1e-4, "dilate": True, "map": False}
+
+    def positive(x, what):
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or not x > 0:
+            raise ValueError('config "adaptive": %s must be a finite number > 0, got %r' % (what, x))
+        return float(x)
+
+    def even(x, what):
+        if isinstance(x, bool) or not isinstance(x, int) or x < 2 or x % 2:
+            raise ValueError('config "adaptive": %s must be an even integer >= 2, got %r' % (what, x))
+        return x
+
+    def flag(x, what):
+        if not isinstance(x, bool):
+            raise ValueError('config "adaptive": %s must be true or false, got %r' % (what, x))
+        return x
+
+    if not isinstance(v, dict):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError('config "adaptive" must be a threshold > 0 or an object, got %r' % (v,))
+        out["threshold"] = positive(v, "the threshold")
+        return out
+    unknown = set(v) - set(out)
+    if unknown:
+        raise ValueError('config "adaptive": unknown keys %r' % (sorted(unknown),))
+    if "threshold" not in v:
+        raise ValueError('config "adaptive" needs "threshold"')
+    out["threshold"] = positive(v["threshold"], '"threshold"')
+    for k in ("min_frames", "batch"):
+        if k in v:
+            out[k] = even(v[k], '"%s"' % k)
+    if "floor" in v:
+        out["floor"] = positive(v["floor"], '"floor"')
+    for k in ("dilate", "map"):
+        if k in v:
+            out[k] = flag(v[k], '"%s"' % k)
+    return out
+
+
 def parse_lens(v):
     """The "lens" extension key of a config entry ->
     {"aperture": R, "focus": F or None, "focus_at": (px, py) or None}.
@@ -247,6 +297,13 @@ class Config:
             if "unbiased" in c and not self.unbiased:
                 raise ValueError('config "roulette" needs the counted history: "unbiased": false cannot go with it')
             self.unbiased = True
+        # "adaptive": <threshold> | {...}: adaptive sampling by half-buffer error (Renderer.render_adaptive),
+        # which runs on the counted history and switches it on; None: every pixel gets every frame
+        self.adaptive = parse_adaptive(c["adaptive"]) if "adaptive" in c else None
+        if self.adaptive:
+            if "unbiased" in c and not self.unbiased:
+                raise ValueError('config "adaptive" needs the counted history: "unbiased": false cannot go with it')
+            self.unbiased = True
         if self.testall:
             self.objs = c["objname"]
             self.objname = ""
@@ -294,6 +351,7 @@ class Config:
     def LENS(self): return self.lens  # extension: parse_lens' dict (thin-lens camera), or None
     def UNBIASED(self): return self.unbiased  # extension: the history counts every sample (on with roulette)
     def ROULETTE(self): return self.roulette  # extension: the depth Russian roulette runs from, 0: none
+    def ADAPTIVE(self): return self.adaptive  # extension: parse_adaptive's dict (adaptive sampling), or None
     def TEXTURES(self): return self.textures  # extension: the model's map_Kd textures on the diffuse lobe
     def CUTOUTS(self): return self.cutouts  # extension: the alpha threshold of the model's cutouts (textures on), or None
     def BUMP(self): return self.bump  # extension: the height maps' slope scale of the model's bump and normal maps, or None

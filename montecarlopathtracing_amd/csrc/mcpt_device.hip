@@ -52,6 +52,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <deque>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -71,6 +72,7 @@
 #include "mcpt_texture.h"  // texture maps: TexRec, texture_factor (shared with mcpt_texture.hip)
 #include "mcpt_bump.h"     // bump and normal maps: BumpRec, bump_normal (shared with mcpt_bump.hip)
 #include "mcpt_lens.h"     // thin-lens camera: LensView, lens_ray (k_render's jittered forms and k_generate_lens)
+#include "mcpt_adaptive.h" // the accessor mcpt_adaptive.hip reaches the context through
 
 using namespace mcpt;
 
@@ -356,6 +358,14 @@ struct mcpt_ctx {
   int32_t entry_log_blocks = 0;
   void *d_denoise = nullptr;              // mcpt_denoise's planes (mcpt_denoise.h), grown on demand
   int64_t denoise_cap = 0;                // pixels
+  int32_t *d_subset_list = nullptr;       // a tile-subset call's active tiles in queue order (k_tile_compact)
+  uint8_t *d_subset_mask = nullptr;       // its mask, one byte per tile
+  int64_t subset_cap = 0;                 // tiles
+  struct MaskUpload {
+    std::vector<uint8_t> host;            // a mask on its way up: reused once `done` has passed
+    hipEvent_t done = nullptr;
+  };
+  std::deque<MaskUpload> mask_uploads;
 };
 
 struct mcpt_state {
@@ -1060,6 +1070,7 @@ struct RenderArgs {
   BumpView bump;              // mapped launches: the scene's normal-map records, indexed like S.tris, and their texel pool (last, likewise)
   float cut_a0;               // textured launches: the scene's cutout threshold (shade_hit's a0), 0: no cutouts (last, likewise)
   int32_t count_all, rr_gate;  // the estimator (mcpt_estimator): count zero samples; shade_hit's rr_gate, max_depth without roulette (last, likewise)
+  uint32_t active_tiles;       // a tile-subset launch (mcpt_render_frames_tiles): tile_order lists this many tiles, the only ones rendered; 0: every tile (last, likewise)
 };
 
 constexpr float kTmin = 0.001f;  // host EPSILON passed as tmin (oclbasic.h:193, scenebuild.cpp:125)
@@ -1341,9 +1352,13 @@ __global__ void __launch_bounds__(64 * kWgWaves, MCPT_WAVES_PER_SIMD) k_render(R
   // (p, b - 1) has published its hand-off record with handoff_tag(tag_base, b).
   // No deadlock: every entry waits only for an entry of the same queue with
   // a lower index, entries are claimed in index order, and a wave starts all
-  // its claimed entries before it claims more.
-  const QueueGeometry geo = queue_geometry(A.W, A.H, A.local_rows, A.tiles_x, A.stripe_rows, A.stripe_index,
-                                           A.stripe_count, A.n_queues, A.spread);
+  // its claimed entries before it claims more.  A tile-subset launch changes
+  // none of that: tile_order then lists the active tiles and their number is
+  // the tile count of everything below (queue_items in the claim, entry_slot,
+  // the spread groups), so entry_slot stays a bijection on n_tiles * 64 slots.
+  QueueGeometry geo = queue_geometry(A.W, A.H, A.local_rows, A.tiles_x, A.stripe_rows, A.stripe_index,
+                                     A.stripe_count, A.n_queues, A.spread);
+  if (A.active_tiles) geo.n_tiles = A.active_tiles;
   const uint32_t nq = A.n_queues;
   uint32_t qs = qs_init(xcc_id(), nq);  // the wave-uniform queue state (mcpt_queue.h, qs_*)
   uint32_t pool = 0, pool_left = 0;     // wave-uniform: claimed, unassigned entries of queue qs_pool_queue(qs)
@@ -2295,8 +2310,10 @@ int mcpt_ctx_destroy(mcpt_ctx *c) {
   if (c->last_pending && c->ev1) (void)hipEventSynchronize(c->ev1);  // the last render may still use the buffers
   for (void *p : {(void *)c->d_queue, (void *)c->d_handoff, (void *)c->d_spill, (void *)c->d_prim, (void *)c->d_prim_tex, (void *)c->d_prim_cost,
                   (void *)c->d_tile_order, (void *)c->d_tile_key, (void *)c->d_wave_log, (void *)c->d_entry_log,
-                  c->d_denoise})
+                  c->d_denoise, (void *)c->d_subset_list, (void *)c->d_subset_mask})
     if (p) (void)hipFree(p);
+  for (auto &u : c->mask_uploads)
+    if (u.done) (void)hipEventDestroy(u.done);
   if (c->ev0) (void)hipEventDestroy(c->ev0);
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->ev_prim) (void)hipEventDestroy(c->ev_prim);
@@ -3235,6 +3252,8 @@ int denoise_scratch(mcpt_ctx *ctx, int64_t n_px, void **scratch, int *device) {
   *scratch = ctx->d_denoise, *device = ctx->device;
   return MCPT_OK;
 }
+// mcpt_adaptive.hip needs the context's GPU alone (mcpt_adaptive.h)
+int adaptive_device(const mcpt_ctx *ctx) { return ctx->device; }
 // mcpt_env.hip reaches a scene's environment through this one (mcpt_env.h)
 int env_scene(const mcpt_scene *scene, EnvView *out, int *on, int *device) {
   *out = scene->env, *on = scene->env_on ? 1 : 0, *device = scene->device;
@@ -4009,6 +4028,87 @@ static int check_estimator(const mcpt_estimator *est) {
 int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_lens *lens,
                            const mcpt_estimator *est, const mcpt_render_params *p, uint32_t *seeds, float *hist,
                            int32_t *count, void *stream) {
+  return mcpt_render_frames_tiles(ctx, scene, cam, lens, est, nullptr, p, seeds, hist, count, stream);
+}
+
+// The active tiles of a tile set in queue order: position i of `order` (null: image order) is kept when its tile's
+// mask byte is set.  One workgroup; each pass scans 1024 positions (a wave scan, then the waves' totals), so the list
+// keeps the order of `order`: dearest first where the view has one, else ascending.  The host counted the set bytes.
+__global__ void __launch_bounds__(1024) k_tile_compact(const int32_t *order, const uint8_t *mask, int32_t n_tiles,
+                                                       int32_t *list) {
+  __shared__ uint32_t wave_sum[16];
+  __shared__ uint32_t base;
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) base = 0;
+  __syncthreads();
+  for (int32_t p0 = 0; p0 < n_tiles; p0 += 1024) {
+    const int32_t pos = p0 + (int32_t)threadIdx.x;
+    const int32_t tile = pos < n_tiles ? (order ? order[pos] : pos) : -1;
+    const bool on = tile >= 0 && tile < n_tiles && mask[tile] != 0;
+    const unsigned long long m = __ballot(on);
+    const uint32_t before = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_sum[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t off = base;
+    for (uint32_t w = 0; w < wave; ++w) off += wave_sum[w];
+    if (on) list[off + before] = tile;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t t = base;
+      for (int w = 0; w < 16; ++w) t += wave_sum[w];
+      base = t;
+    }
+    __syncthreads();
+  }
+}
+
+// A tile set's mask, checked and counted: MCPT_ERR_ARG for a null mask, a wrong n_tiles or a striped call.
+static int check_tile_set(const mcpt_tile_set *tiles, const mcpt_render_params *p, int64_t *active) {
+  *active = 0;
+  if (!tiles) return MCPT_OK;
+  const int64_t want = (int64_t)((p->width + 7) / 8) * ((p->height + 7) / 8);
+  if (!tiles->mask) return mcpt::fail(MCPT_ERR_ARG, "render: a tile set needs a mask");
+  if (tiles->n_tiles != want) return mcpt::fail(MCPT_ERR_ARG, "render: tile set n_tiles is not ceil(W/8) * ceil(H/8)");
+  if (p->stripe_count != 1) return mcpt::fail(MCPT_ERR_ARG, "render: a tile set needs stripe_count = 1");
+  for (int64_t t = 0; t < want; ++t) *active += tiles->mask[t] != 0;
+  return MCPT_OK;
+}
+
+// The list of a subset call, built behind the call's other work on `st`: the mask goes up from a context-owned
+// host copy (the caller's pointer is not kept) that is reused only once an event behind its copy has passed, and
+// k_tile_compact filters the call's tile order (A.tile_order, null: image order) into the context's list.  Mask
+// and list live in the context like the queue heads and the hand-off area: calls on one stream follow each other.
+static int subset_list(mcpt_ctx *ctx, const mcpt_tile_set *tiles, int64_t active, hipStream_t st, RenderArgs &A) {
+  const int64_t n = tiles->n_tiles;
+  mcpt_ctx::MaskUpload *slot = nullptr;
+  for (auto &u : ctx->mask_uploads)
+    if (hipEventQuery(u.done) == hipSuccess) {
+      slot = &u;
+      break;
+    }
+  if (!slot) {
+    ctx->mask_uploads.emplace_back();
+    slot = &ctx->mask_uploads.back();
+    if (hipEventCreateWithFlags(&slot->done, hipEventDisableTiming) != hipSuccess) {
+      ctx->mask_uploads.pop_back();
+      return mcpt::fail(MCPT_ERR_HIP, "render: no event for the tile mask upload");
+    }
+  }
+  slot->host.assign(tiles->mask, tiles->mask + n);
+  MCPT_TRY(grow_dev(ctx->subset_cap, n, (void **)&ctx->d_subset_list, sizeof(int32_t), (void **)&ctx->d_subset_mask, 1));
+  HIP_OK(hipMemcpyAsync(ctx->d_subset_mask, slot->host.data(), (size_t)n, hipMemcpyHostToDevice, st));
+  HIP_OK(hipEventRecord(slot->done, st));
+  hipLaunchKernelGGL(k_tile_compact, dim3(1), dim3(1024), 0, st, A.tile_order, ctx->d_subset_mask, (int32_t)n,
+                     ctx->d_subset_list);
+  HIP_OK(hipGetLastError());
+  A.tile_order = ctx->d_subset_list;
+  A.active_tiles = (uint32_t)active;
+  return MCPT_OK;
+}
+
+int mcpt_render_frames_tiles(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_camera *cam, const mcpt_lens *lens,
+                             const mcpt_estimator *est, const mcpt_tile_set *tiles, const mcpt_render_params *p,
+                             uint32_t *seeds, float *hist, int32_t *count, void *stream) {
   if (!ctx || !scene || !cam || !p || !seeds || !hist || !count) return mcpt::fail(MCPT_ERR_ARG, "render: null argument");
   MCPT_TRY(check_render(p));
   MCPT_TRY(check_lens(lens, "render"));
@@ -4017,9 +4117,22 @@ int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ca
   if (lens_on && p->jitter != 1) return mcpt::fail(MCPT_ERR_ARG, "render: a lens needs params->jitter = 1");
   if (scene->cut_a0 > 0.0f && p->max_depth > 255)
     return mcpt::fail(MCPT_ERR_ARG, "render: max_depth above 255 on a scene with cutouts");
+  int64_t active = 0;
+  MCPT_TRY(check_tile_set(tiles, p, &active));
+  // a full set is the whole-image call; the plan and the kernel see a subset only where it is a proper one
+  const bool subset = tiles && active < tiles->n_tiles;
   HIP_OK(hipSetDevice(ctx->device));
   hipStream_t st = (hipStream_t)stream;
+  if (subset && active == 0) {  // nothing to render: no launch, no state touched; the stats of a call that ran nothing
+    HIP_OK(hipEventRecord(ctx->ev0, st));
+    HIP_OK(hipEventRecord(ctx->ev1, st));
+    std::memset(&ctx->last, 0, sizeof(ctx->last));
+    ctx->last_pending = true;
+    ctx->last_stats = false;
+    return MCPT_OK;
+  }
   RenderArgs A;
+  A.active_tiles = 0;
   A.cam = *cam;
   A.S = scene->view;
   A.env = scene->env;
@@ -4052,7 +4165,7 @@ int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ca
   const mcpt::PlanOut P = mcpt::plan_launches(
       {p->width, p->height, p->frames, p->frames_per_launch, p->stripe_rows, p->stripe_index, p->stripe_count,
        T.block_entries, T.max_block_frames, T.last_block_frames, T.pixel_spread,
-       (int64_t)std::max(K.per_cu, 1) * ctx->n_cu, kWgWaves});
+       (int64_t)std::max(K.per_cu, 1) * ctx->n_cu, kWgWaves, subset ? active : 0});
   A.local_rows = P.local_rows, A.tiles_x = P.tiles_x, A.spread = P.spread;
   A.fpl = P.fpl_head, A.nb_head = P.nb_head, A.fpl_tail = P.fpl_tail;
   // spill areas; kQueues heads per launch (+ the primary pass), zeroed by memsets; hand-off granules
@@ -4077,7 +4190,8 @@ int mcpt_render_frames_est(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ca
     HIP_OK(hipMemsetAsync(ctx->d_stats, 0, kStatSlots * sizeof(unsigned long long), st));
   HIP_OK(hipEventRecord(ctx->ev0, st));
   int prim_state = 0, launches = 0;
-  MCPT_TRY(primary_cache(ctx, scene, cam, p, K, P, st, A, &prim_state));
+  MCPT_TRY(primary_cache(ctx, scene, cam, p, K, P, st, A, &prim_state));  // whole-view, subset or not
+  if (subset && p->frames > 0) MCPT_TRY(subset_list(ctx, tiles, active, st, A));
   if (K.kind == 3) {  // the render launches search the 96-B tree: its arrays, tri4's indices (k_render, FMT)
     A.S.near4 = reinterpret_cast<const DevNode4 *>(scene->near4x), A.S.nodes4 = scene->nodes4x, A.S.tris = scene->tri4;
     A.S.n_tris = 4 * (int64_t)scene->view.n_near4;

@@ -19,6 +19,10 @@ struct PlanIn {
   int32_t block_entries, max_block_frames, last_block_frames, pixel_spread;  // mcpt_tuning
   int64_t resident_wg;  // workgroups resident at once: max(per_cu, 1) * n_cu
   int32_t wg_waves;     // waves per workgroup
+  // a tile-subset call (mcpt_render_frames_tiles): the tiles it renders, 0: all.  It takes the
+  // tile count's place in the grid, the queue items, pixels per lane, block sizing and spread;
+  // local_rows, tiles_x and tiles stay the whole view's (the primary-hit pass is whole-view)
+  int64_t active_tiles = 0;
 };
 
 struct PlanOut {
@@ -40,8 +44,9 @@ inline PlanOut plan_launches(const PlanIn &in) {
   o.local_rows = full * in.stripe_rows + extra;
   o.tiles_x = (in.width + 7) / 8;
   o.tiles = (int64_t)o.tiles_x * ((o.local_rows + 7) / 8);
+  const int64_t run_tiles = in.active_tiles > 0 ? in.active_tiles : o.tiles;  // the tiles the launches render
   // grid_wg workgroups of wg_waves waves: `grid` waves (a tile per wave at most)
-  o.grid_wg = std::max<int64_t>(1, std::min<int64_t>((o.tiles + in.wg_waves - 1) / in.wg_waves, in.resident_wg));
+  o.grid_wg = std::max<int64_t>(1, std::min<int64_t>((run_tiles + in.wg_waves - 1) / in.wg_waves, in.resident_wg));
   const int64_t grid = o.grid_wg * in.wg_waves;
   // frames_per_launch = frames per BLOCK: a lane runs one pixel for one block
   // of frames, then hands the pixel's state to whichever lane takes its next
@@ -61,7 +66,7 @@ inline PlanOut plan_launches(const PlanIn &in) {
   // boundary becomes a wait for the slowest pixel of the previous block, so
   // blocks there keep at least 4 frames (measured on C2 and C4 shares of 2,
   // 4 and 8 ranks, tools/sweep.py --stripes).
-  const uint32_t n_items = (uint32_t)o.tiles_x * (uint32_t)((o.local_rows + 7) / 8) * 64u;
+  const uint32_t n_items = (uint32_t)run_tiles * 64u;
   const int cap = in.max_block_frames > 0 ? in.max_block_frames : 32;  // frames per block at most (auto plans)
   int fpl = in.frames_per_launch;
   bool tail_ok = false;  // auto plan with several entries per lane: a short last block may apply

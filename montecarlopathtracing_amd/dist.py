@@ -61,9 +61,17 @@ def reduce_image(hist, count, seeds, mask, group=None, dst=0):
     return h, flat[:, 4].contiguous(), flat[:, 5].to(torch.int64) & 0xFFFFFFFF
 
 
+def refuse_adaptive(adaptive):
+    """Adaptive sampling (Renderer.render_adaptive) is single-GPU: its tile subsets are not defined on a
+    row-striped share.  ValueError for anything but None / False."""
+    if adaptive is not None and adaptive is not False:
+        raise ValueError("adaptive sampling is not available on the distributed path: a tile subset of a "
+                         "row-striped share is not defined; render on one GPU, or drop \"adaptive\" / --adaptive")
+
+
 def render_distributed(renderer, scene, camera, width, height, max_depth, max_attempt, frames, seeds,
                        stripe_rows=16, group=None, mode=0, jitter=False, vertex_normals=None, textures=None,
-                       lens=None, bump=None, cutouts=None, unbiased=False, roulette=0):
+                       lens=None, bump=None, cutouts=None, unbiased=False, roulette=0, adaptive=None):
     """Render the whole image across the process group; rank 0 gets the image.
     `jitter`: Renderer.render_frames' sub-pixel jitter (per-pixel draws, so
     still the single-GPU image for any GPU count).  `vertex_normals`: smooth
@@ -79,7 +87,10 @@ def render_distributed(renderer, scene, camera, width, height, max_depth, max_at
     rank's scene after the textures (Renderer.set_texture_alpha).  `unbiased`,
     `roulette`: Renderer.render_frames' estimator on every rank (each pixel
     belongs to one rank and draws from its own chain, so striping changes no bit).
+    `adaptive`: refused (ValueError) unless None or False: adaptive sampling renders
+    subsets of whole-image tiles, which a striped share does not have.
     Returns (hist, count, seeds) as numpy on rank 0, None elsewhere."""
+    refuse_adaptive(adaptive)
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     if vertex_normals is not None:
         renderer.set_vertex_normals(scene, vertex_normals)

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import adaptive as AD
 
 
 def _stream():
@@ -150,6 +151,17 @@ class ImageState:
 
     def seeds_np(self):
         return self.seeds.cpu().numpy().view(np.uint32)
+
+
+class _HalfState:
+    """One half history of an adaptive render: its own mean and count on the parent state's seed chain."""
+
+    def __init__(self, state):
+        self.width, self.height = state.width, state.height
+        self.seeds = state.seeds
+        self.hist = torch.zeros_like(state.hist)
+        self.count = torch.zeros_like(state.count)
+        self.frames_done = 0
 
 
 class Renderer:
@@ -312,7 +324,8 @@ class Renderer:
     # ---------------------------------------------------------- fused path
     def render_frames(self, scene, camera, state, max_depth, max_attempt, frames, frame_begin=None,
                       stripe_rows=16, stripe_index=0, stripe_count=1, mode=L.MODE_EXACT,
-                      frames_per_launch=0, schedule=None, jitter=None, lens=None, unbiased=False, roulette=0):
+                      frames_per_launch=0, schedule=None, jitter=None, lens=None, unbiased=False, roulette=0,
+                      tiles=None):
         """Frames [frame_begin, frame_begin+frames) for this GPU's row stripes
         (OpenCL::update x frames + ColorOut accumulation).  `schedule`
         (L.SCHED_*; default: the scene's, see tune_schedule) only changes speed.
@@ -332,7 +345,16 @@ class Renderer:
         0: off): Russian roulette on diffuse and glossy bounces from that depth
         on, the survival probability the bounce's albedo.  A path it ends is a
         zero sample that has to be counted: roulette > 0 with unbiased=False is
-        a ValueError."""
+        a ValueError.
+        `tiles` (opt-in; mcpt_render_frames_tiles): a mask with one entry per 8x8
+        tile, row-major over ceil(W/8) x ceil(H/8); only the tiles with a nonzero
+        entry are rendered, each of their pixels exactly as the whole-image call
+        renders it, and no other pixel's state is read or written.  None: every
+        tile.  Its length is checked by the library; it needs stripe_count = 1."""
+        tiles_c = tile_mask = None
+        if tiles is not None:
+            tile_mask = np.ascontiguousarray(np.asarray(tiles).reshape(-1) != 0, np.uint8)
+            tiles_c = L.TileSet(tile_mask.ctypes.data, len(tile_mask), 0)
         est_c = _estimator_struct(unbiased, roulette)
         lens_c = _lens_struct(lens)
         if lens_c is not None:
@@ -352,7 +374,13 @@ class Renderer:
         p.schedule = int(getattr(scene, "schedule", L.SCHED_PAIRED) if schedule is None else schedule)
         p.jitter = int(jitter)
         cam = np.ascontiguousarray(camera)
-        if est_c is not None:
+        if tiles_c is not None:
+            L.check(L.lib().mcpt_render_frames_tiles(self.ctx, scene.handle, L.ptr(cam),
+                                                     None if lens_c is None else ctypes.byref(lens_c),
+                                                     None if est_c is None else ctypes.byref(est_c),
+                                                     ctypes.byref(tiles_c), ctypes.byref(p), L.ptr(state.seeds),
+                                                     L.ptr(state.hist), L.ptr(state.count), _stream()))
+        elif est_c is not None:
             L.check(L.lib().mcpt_render_frames_est(self.ctx, scene.handle, L.ptr(cam),
                                                    None if lens_c is None else ctypes.byref(lens_c),
                                                    ctypes.byref(est_c), ctypes.byref(p), L.ptr(state.seeds),
@@ -366,6 +394,85 @@ class Renderer:
                                                L.ptr(state.hist), L.ptr(state.count), _stream()))
         state.frames_done = p.frame_begin + p.frames
         return state
+
+    # ---------------------------------------------------------- adaptive sampling
+    def tile_error(self, width, height, hist_a, count_a, hist_b, count_b, floor=1e-4):
+        """mcpt_tile_error: the half-buffer error estimate of every 8x8 tile of
+        two half histories (device tensors as ImageState keeps them), a float32
+        device tensor of ceil(W/8) * ceil(H/8), row-major."""
+        tx, ty = AD.tile_grid(width, height)
+        err = torch.empty(tx * ty, dtype=torch.float32, device=self.device)
+        L.check(L.lib().mcpt_tile_error(self.ctx, int(width), int(height), L.ptr(hist_a), L.ptr(count_a), L.ptr(hist_b),
+                                        L.ptr(count_b), float(floor), L.ptr(err), _stream()))
+        return err
+
+    def merge_halves(self, hist_a, count_a, hist_b, count_b, hist_out=None, count_out=None):
+        """mcpt_merge_halves: the count-weighted mean and the summed count of two
+        half histories, into (hist_out, count_out) (new tensors when None)."""
+        n = count_a.numel()
+        if hist_out is None:
+            hist_out = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+        if count_out is None:
+            count_out = torch.empty(n, dtype=torch.int32, device=self.device)
+        L.check(L.lib().mcpt_merge_halves(self.ctx, L.ptr(hist_a), L.ptr(count_a), L.ptr(hist_b), L.ptr(count_b), n,
+                                          L.ptr(hist_out), L.ptr(count_out), _stream()))
+        return hist_out, count_out
+
+    def render_adaptive(self, scene, camera, state, max_depth, frames, threshold, min_frames=16, batch=8, floor=1e-4,
+                        dilate=True, jitter=None, lens=None, roulette=0, mode=L.MODE_EXACT, schedule=None):
+        """Adaptive sampling (opt-in, no reference counterpart): at most `frames`
+        frames per pixel, spent where the image is noisy.  Frames go alternately
+        into two half histories A and B that share `state`'s seed chain; round 0
+        renders min_frames / 2 frames into A and then into B on every tile; each
+        later round reads mcpt_tile_error of the halves, marks the tiles above
+        `threshold` (adaptive.select_tiles; `dilate` adds their neighbours),
+        stops when none is left or the budget is spent, and else renders
+        min(batch, frames - issued) / 2 frames into A and then into B on those
+        tiles alone (render_frames' `tiles`).  The history counts every sample
+        (`unbiased` is always on).  At the end mcpt_merge_halves writes
+        state.hist and state.count; state.frames_done is the frames issued.
+        `state` must be fresh (frames_done == 0); frames, min_frames and batch
+        are even with 2 <= min_frames <= frames; threshold >= 0 (inf: round 0
+        alone; 0: every round whole-image while any tile's halves differ).  A
+        ValueError otherwise, before any C call.  Returns an
+        adaptive.AdaptiveReport.  Adaptive stopping is not exactly unbiased: a
+        tile stops on a noisy estimate of its own error."""
+        AD.check_arguments(frames, threshold, min_frames, batch, floor)
+        if state.frames_done != 0:
+            raise ValueError("render_adaptive: the state must be fresh (frames_done == 0), got %d" % state.frames_done)
+        _roulette_depth(roulette)
+        _lens_struct(lens)
+        w, h = state.width, state.height
+        halves = [_HalfState(state), _HalfState(state)]
+        rep = AD.AdaptiveReport(w, h, int(frames))
+        kw = dict(mode=mode, schedule=schedule, jitter=jitter, lens=lens, unbiased=True, roulette=roulette)
+
+        def issue(n, mask):
+            for half in halves:  # A, then B, on the one seed chain
+                self.render_frames(scene, camera, half, max_depth, int(frames), n // 2, frame_begin=half.frames_done,
+                                   tiles=mask, **kw)
+            rep.round_frames.append(n)
+            rep.frames_issued += n
+
+        issue(int(min_frames), None)
+        while True:
+            n = AD.round_frames(rep.frames_issued, frames, batch)
+            if n == 0:
+                break
+            a, b = halves
+            err = self.tile_error(w, h, a.hist, a.count, b.hist, b.count, floor).cpu().numpy()
+            mask = AD.select_tiles(err, threshold, rep.tiles_x, rep.tiles_y, dilate)
+            rep.errors.append(err.reshape(rep.tiles_y, rep.tiles_x))
+            rep.masks.append(mask.reshape(rep.tiles_y, rep.tiles_x))
+            if not mask.any():
+                break
+            issue(n, mask)
+        a, b = halves
+        self.merge_halves(a.hist, a.count, b.hist, b.count, state.hist, state.count)
+        state.frames_done = rep.frames_issued
+        rep.samples = int(state.count.sum(dtype=torch.int64).item())
+        rep.fraction = rep.samples / float(w * h * int(frames))
+        return rep
 
     def tune_schedule(self, scene, camera, state, max_depth, max_attempt, frames=64, trials=1, **kw):
         """Pick the faster leaf-test schedule for this scene and view: render
