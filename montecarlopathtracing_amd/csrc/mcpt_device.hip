@@ -43,6 +43,16 @@
 //    mapped forms sit on the textured forms and are compiled in a fourth
 //    translation unit (mcpt_render_bump.hip: this file with MCPT_BUMP_TU and
 //    the one table bump_render_fn).
+//
+// The three tables have one body (MCPT_RENDER_TABLE) and differ in k_render's
+// trailing template arguments alone.  A scene's level (scene_level: 0 plain, 1
+// vertex normals, 2 textures, 3 normal maps) picks the table, and k_primary's
+// and k_intersect's form through [level][mode] tables.  The setters of the
+// per-triangle attributes (vertex normals, textures, normal maps) keep their
+// own rules and share the rest: the host half of textures and maps in
+// mcpt_attr.h (no HIP, checked on the CPU), an owning device buffer (DevBuf),
+// one upload with the tri4-ordered copy of the 96-B launches (upload_attr,
+// k_relabel<Rec>) and one commit (commit_attr).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -73,6 +83,7 @@
 #include "mcpt_bump.h"     // bump and normal maps: BumpRec, bump_normal (shared with mcpt_bump.hip)
 #include "mcpt_lens.h"     // thin-lens camera: LensView, lens_ray (k_render's jittered forms and k_generate_lens)
 #include "mcpt_adaptive.h" // the accessor mcpt_adaptive.hip reaches the context through
+#include "mcpt_attr.h"     // the setters' host half: image pools, range checks, TexRec and BumpRec packing (no HIP)
 
 using namespace mcpt;
 
@@ -1874,54 +1885,26 @@ const void *texture_render_fn(int kind, int stats, int win, int pair, int jitter
 // MCPT_BUMP_TU build of this file (mcpt_render_bump.hip) and reached through
 // this table alone: the same indices.
 const void *bump_render_fn(int kind, int stats, int win, int pair, int jitter, int env);
+// The body of such a table, once: NAME's k_render forms are the N forms with the trailing template arguments `...`.
+#define MCPT_NE(M, ST, W, P, QN, J, ...) {(const void *)k_render<M, ST, W, P, QN, false, true, J, false, __VA_ARGS__>, \
+                                          (const void *)k_render<M, ST, W, P, QN, false, true, J, true, __VA_ARGS__>}
+#define MCPT_NJ(M, ST, W, P, QN, ...) {MCPT_NE(M, ST, W, P, QN, false, __VA_ARGS__), MCPT_NE(M, ST, W, P, QN, true, __VA_ARGS__)}
+#define MCPT_NW(M, ST, W, QN, ...) {MCPT_NJ(M, ST, W, false, QN, __VA_ARGS__), MCPT_NJ(M, ST, W, true, QN, __VA_ARGS__)}
+#define MCPT_NK(M, QN, ...) {{MCPT_NW(M, false, false, QN, __VA_ARGS__), MCPT_NW(M, false, true, QN, __VA_ARGS__)}, \
+                             {MCPT_NW(M, true, false, QN, __VA_ARGS__), MCPT_NW(M, true, true, QN, __VA_ARGS__)}}
+#define MCPT_RENDER_TABLE(NAME, ...)                                                                                  \
+  const void *NAME(int kind, int stats, int win, int pair, int jitter, int env) {                                     \
+    static const void *const fns[4][2][2][2][2][2] = {                                                                \
+        MCPT_NK(MCPT_MODE_EXACT, kFmt128, __VA_ARGS__), MCPT_NK(MCPT_MODE_NOPRUNE, kFmt128, __VA_ARGS__),             \
+        MCPT_NK(MCPT_MODE_EXACT, kFmtQ, __VA_ARGS__), MCPT_NK(MCPT_MODE_EXACT, kFmt96, __VA_ARGS__)};                 \
+    return fns[kind & 3][stats & 1][win & 1][pair & 1][jitter & 1][env & 1];                                          \
+  }
 #if defined(MCPT_BUMP_TU)
-const void *bump_render_fn(int kind, int stats, int win, int pair, int jitter, int env) {
-#define MCPT_NE(M, ST, W, P, QN, J) {(const void *)k_render<M, ST, W, P, QN, false, true, J, false, true, true, true>, \
-                                     (const void *)k_render<M, ST, W, P, QN, false, true, J, true, true, true, true>}
-#define MCPT_NJ(M, ST, W, P, QN) {MCPT_NE(M, ST, W, P, QN, false), MCPT_NE(M, ST, W, P, QN, true)}
-#define MCPT_NW(M, ST, W, QN) {MCPT_NJ(M, ST, W, false, QN), MCPT_NJ(M, ST, W, true, QN)}
-#define MCPT_NK(M, QN) {{MCPT_NW(M, false, false, QN), MCPT_NW(M, false, true, QN)}, \
-                        {MCPT_NW(M, true, false, QN), MCPT_NW(M, true, true, QN)}}
-  static const void *const fns[4][2][2][2][2][2] = {MCPT_NK(MCPT_MODE_EXACT, kFmt128), MCPT_NK(MCPT_MODE_NOPRUNE, kFmt128),
-                                                    MCPT_NK(MCPT_MODE_EXACT, kFmtQ), MCPT_NK(MCPT_MODE_EXACT, kFmt96)};
-#undef MCPT_NK
-#undef MCPT_NW
-#undef MCPT_NJ
-#undef MCPT_NE
-  return fns[kind & 3][stats & 1][win & 1][pair & 1][jitter & 1][env & 1];
-}
+MCPT_RENDER_TABLE(bump_render_fn, true, true, true)
 #elif defined(MCPT_TEXTURE_TU)
-const void *texture_render_fn(int kind, int stats, int win, int pair, int jitter, int env) {
-#define MCPT_NE(M, ST, W, P, QN, J) {(const void *)k_render<M, ST, W, P, QN, false, true, J, false, true, true>, \
-                                     (const void *)k_render<M, ST, W, P, QN, false, true, J, true, true, true>}
-#define MCPT_NJ(M, ST, W, P, QN) {MCPT_NE(M, ST, W, P, QN, false), MCPT_NE(M, ST, W, P, QN, true)}
-#define MCPT_NW(M, ST, W, QN) {MCPT_NJ(M, ST, W, false, QN), MCPT_NJ(M, ST, W, true, QN)}
-#define MCPT_NK(M, QN) {{MCPT_NW(M, false, false, QN), MCPT_NW(M, false, true, QN)}, \
-                        {MCPT_NW(M, true, false, QN), MCPT_NW(M, true, true, QN)}}
-  static const void *const fns[4][2][2][2][2][2] = {MCPT_NK(MCPT_MODE_EXACT, kFmt128), MCPT_NK(MCPT_MODE_NOPRUNE, kFmt128),
-                                                    MCPT_NK(MCPT_MODE_EXACT, kFmtQ), MCPT_NK(MCPT_MODE_EXACT, kFmt96)};
-#undef MCPT_NK
-#undef MCPT_NW
-#undef MCPT_NJ
-#undef MCPT_NE
-  return fns[kind & 3][stats & 1][win & 1][pair & 1][jitter & 1][env & 1];
-}
+MCPT_RENDER_TABLE(texture_render_fn, true, true)
 #elif defined(MCPT_SMOOTH_TU)
-const void *smooth_render_fn(int kind, int stats, int win, int pair, int jitter, int env) {
-#define MCPT_NE(M, ST, W, P, QN, J) {(const void *)k_render<M, ST, W, P, QN, false, true, J, false, true>, \
-                                     (const void *)k_render<M, ST, W, P, QN, false, true, J, true, true>}
-#define MCPT_NJ(M, ST, W, P, QN) {MCPT_NE(M, ST, W, P, QN, false), MCPT_NE(M, ST, W, P, QN, true)}
-#define MCPT_NW(M, ST, W, QN) {MCPT_NJ(M, ST, W, false, QN), MCPT_NJ(M, ST, W, true, QN)}
-#define MCPT_NK(M, QN) {{MCPT_NW(M, false, false, QN), MCPT_NW(M, false, true, QN)}, \
-                        {MCPT_NW(M, true, false, QN), MCPT_NW(M, true, true, QN)}}
-  static const void *const fns[4][2][2][2][2][2] = {MCPT_NK(MCPT_MODE_EXACT, kFmt128), MCPT_NK(MCPT_MODE_NOPRUNE, kFmt128),
-                                                    MCPT_NK(MCPT_MODE_EXACT, kFmtQ), MCPT_NK(MCPT_MODE_EXACT, kFmt96)};
-#undef MCPT_NK
-#undef MCPT_NW
-#undef MCPT_NJ
-#undef MCPT_NE
-  return fns[kind & 3][stats & 1][win & 1][pair & 1][jitter & 1][env & 1];
-}
+MCPT_RENDER_TABLE(smooth_render_fn, true)
 #else  // everything below is the main translation unit's alone
 
 // ------------------------------------------------------ wavefront kernels
@@ -3262,9 +3245,102 @@ int env_scene(const mcpt_scene *scene, EnvView *out, int *on, int *device) {
 }  // namespace mcpt
 }  // extern "C++"
 
+// ------------------------------------------------- scene attributes: shared plumbing
+extern "C++" {
+// what every setter asks of its handles first
+static int check_handles(const char *who, const mcpt_ctx *ctx, const mcpt_scene *scene) {
+  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, std::string(who) + ": null context or scene");
+  if (ctx->device != scene->device) return mcpt::fail(MCPT_ERR_ARG, std::string(who) + ": scene and context are on different GPUs");
+  return MCPT_OK;
+}
+
+// A device allocation a setter owns until it hands it to the scene: freed on
+// scope exit, so a call that fails anywhere leaves nothing allocated.
+struct DevBuf {
+  void *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t bytes) {
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  void *release() {
+    void *r = p;
+    p = nullptr;
+    return r;
+  }
+};
+
+// `bytes` of host memory in a new allocation of b; the messages are the setter's (`who`)
+static int upload_bytes(const char *who, DevBuf &b, const void *host, size_t bytes) {
+  hipError_t e = b.alloc(bytes);
+  if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string(who) + ": allocation: " + hipGetErrorString(e));
+  e = hipMemcpy(b.p, host, bytes, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string(who) + ": upload: " + hipGetErrorString(e));
+  return MCPT_OK;
+}
+
+// tri4-ordered records from the reference-ordered ones: slot k of tri4 carries
+// its reference triangle's id in aux.y (tri4_record); an empty slot (all zeros,
+// never hit) reads as triangle 0 and takes its record, any other id (not a
+// record tri4_record wrote) the attribute's `empty` one
+template <class Rec>
+__global__ void __launch_bounds__(256) k_relabel(const DevTri *__restrict__ tri4, int64_t n4, int64_t n_tris,
+                                                 const Rec *__restrict__ rec, Rec *__restrict__ rec4, Rec empty) {
+  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (k >= n4) return;
+  const int64_t t = (int64_t)mcpt::n96_bits(tri4[k].aux.y);
+  rec4[k] = t < n_tris ? rec[t] : empty;
+}
+
+// A per-triangle attribute's two arrays: `rec` (n_tris records of Rec's bytes,
+// reference order; null: the attribute is being cleared, both stay empty) into
+// a, and its tri4-ordered copy into a4 where the scene has the 96-B nodes.
+// First waits for the renders already enqueued, which may still read the
+// previous arrays (`old`), before anything is allocated.
+template <class Rec>
+static int upload_attr(const char *who, const mcpt_scene *scene, const void *old, const void *rec, Rec empty, DevBuf &a,
+                       DevBuf &a4) {
+  if (old) HIP_OK(hipDeviceSynchronize());
+  if (!rec) return MCPT_OK;
+  const int64_t n = scene->n_tris;
+  MCPT_TRY(upload_bytes(who, a, rec, (size_t)n * sizeof(Rec)));
+  if (!scene->tri4) return MCPT_OK;
+  const int64_t n4 = 4 * (int64_t)scene->view.n_near4;
+  hipError_t e = a4.alloc((size_t)n4 * sizeof(Rec));
+  if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string(who) + ": allocation: " + hipGetErrorString(e));
+  hipLaunchKernelGGL(k_relabel<Rec>, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, scene->tri4, n4, n,
+                     (const Rec *)a.p, (Rec *)a4.p, empty);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string(who) + ": relabel: " + hipGetErrorString(e));
+  return MCPT_OK;
+}
+
+// The commit of a validated, uploaded attribute: each of the scene's arrays
+// (`slot`) is freed and takes its new allocation (null: cleared); the
+// primary-hit records of any context are those of another scene now.
+struct AttrSlot {
+  void **slot;
+  DevBuf *now;
+};
+static void commit_attr(mcpt_ctx *ctx, mcpt_scene *scene, std::initializer_list<AttrSlot> slots) {
+  for (const AttrSlot &s : slots) {
+    if (*s.slot) (void)hipFree(*s.slot);
+    *s.slot = s.now->release();
+  }
+  ++scene->vn_epoch;
+  ctx->prim_valid = false;
+}
+}  // extern "C++"
+
 int mcpt_scene_set_environment(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_environment *env) {
-  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_environment: null context or scene");
-  if (ctx->device != scene->device) return mcpt::fail(MCPT_ERR_ARG, "set_environment: scene and context are on different GPUs");
+  MCPT_TRY(check_handles("set_environment", ctx, scene));
   // validate everything before anything changes: a failed call leaves the scene's environment as it was
   EnvView v = {};
   std::vector<f4> texels;
@@ -3295,45 +3371,25 @@ int mcpt_scene_set_environment(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_envi
   // renders already enqueued may still read the previous map: wait for them
   // before anything is allocated, so a failure leaves nothing behind
   if (scene->env_map) HIP_OK(hipDeviceSynchronize());
-  f4 *map = nullptr;
+  DevBuf map;
   if (!texels.empty()) {
-    HIP_OK(hipMalloc((void **)&map, texels.size() * sizeof(f4)));
-    const hipError_t e = hipMemcpy(map, texels.data(), texels.size() * sizeof(f4), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(map);
-      return mcpt::fail(MCPT_ERR_HIP, std::string("set_environment: map upload: ") + hipGetErrorString(e));
-    }
+    HIP_OK(map.alloc(texels.size() * sizeof(f4)));
+    const hipError_t e = hipMemcpy(map.p, texels.data(), texels.size() * sizeof(f4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string("set_environment: map upload: ") + hipGetErrorString(e));
   }
   if (scene->env_map) (void)hipFree(scene->env_map);
-  v.map = map;
-  scene->env_map = map;
+  scene->env_map = (f4 *)map.release();
+  v.map = scene->env_map;
   scene->env = v;
   scene->env_on = env != nullptr;
   return MCPT_OK;
 }
 
-// tri4-ordered vertex normals from the reference-ordered ones: slot k of tri4
-// carries its reference triangle's id in aux.y (tri4_record); an empty slot
-// (all zeros, never hit) reads as triangle 0 and takes its normals
-__global__ void __launch_bounds__(256) k_vnrm_relabel(const DevTri *__restrict__ tri4, int64_t n4, int64_t n_tris,
-                                                      const VtxNormals *__restrict__ vn, VtxNormals *__restrict__ vn4) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= n4) return;
-  const int64_t t = (int64_t)mcpt::n96_bits(tri4[k].aux.y);
-  VtxNormals r;
-  if (t >= n_tris) {  // (not a record tri4_record wrote)
-    r.q[0] = (f4){0.0f, 0.0f, 0.0f, 1.0f};
-    r.q[1] = r.q[2] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-  } else {
-    r = vn[t];
-  }
-  vn4[k] = r;
-}
+// the record of a flat triangle, and of a tri4 slot that is no triangle's: shading_normal returns the face normal
+static const VtxNormals kFlatNormals = {{{0.0f, 0.0f, 0.0f, 1.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}}};
 
 int mcpt_scene_set_vertex_normals(mcpt_ctx *ctx, mcpt_scene *scene, const float *vn) {
-  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_vertex_normals: null context or scene");
-  if (ctx->device != scene->device)
-    return mcpt::fail(MCPT_ERR_ARG, "set_vertex_normals: scene and context are on different GPUs");
+  MCPT_TRY(check_handles("set_vertex_normals", ctx, scene));
   HIP_OK(hipSetDevice(scene->device));
   const int64_t n = scene->n_tris;
   // validate everything before anything changes: a failed call leaves the scene's vertex normals as they were
@@ -3354,42 +3410,13 @@ int mcpt_scene_set_vertex_normals(mcpt_ctx *ctx, mcpt_scene *scene, const float 
                                               std::to_string(i) + ")");
       }
       VtxNormals &r = rec[(size_t)i];
-      if (flat) {  // never interpolated (its normal may be a degenerate triangle's NaN): no value kept
-        r.q[0] = (f4){0.0f, 0.0f, 0.0f, 1.0f};
-        r.q[1] = r.q[2] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-      } else {
-        for (int k = 0; k < 3; ++k) r.q[k] = (f4){v[3 * k], v[3 * k + 1], v[3 * k + 2], 0.0f};
-      }
+      r = kFlatNormals;  // a flat one is never interpolated (its normal may be a degenerate triangle's NaN): no value kept
+      for (int k = 0; k < 3 && !flat; ++k) r.q[k] = (f4){v[3 * k], v[3 * k + 1], v[3 * k + 2], 0.0f};
     }
   }
-  // renders already enqueued may still read the previous arrays: wait for them
-  if (scene->vnrm || scene->vnrm4) HIP_OK(hipDeviceSynchronize());
-  VtxNormals *a = nullptr, *a4 = nullptr;
-  if (vn) {
-    auto undo = [&](const std::string &what, hipError_t e) {
-      if (a) (void)hipFree(a);
-      if (a4) (void)hipFree(a4);
-      return mcpt::fail(MCPT_ERR_HIP, "set_vertex_normals: " + what + ": " + hipGetErrorString(e));
-    };
-    hipError_t e = hipMalloc((void **)&a, (size_t)n * sizeof(VtxNormals));
-    if (e != hipSuccess) return a = nullptr, undo("allocation", e);
-    e = hipMemcpy(a, rec.data(), (size_t)n * sizeof(VtxNormals), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return undo("upload", e);
-    if (scene->tri4) {
-      const int64_t n4 = 4 * (int64_t)scene->view.n_near4;
-      e = hipMalloc((void **)&a4, (size_t)n4 * sizeof(VtxNormals));
-      if (e != hipSuccess) return a4 = nullptr, undo("allocation", e);
-      hipLaunchKernelGGL(k_vnrm_relabel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, scene->tri4, n4, n, a, a4);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) return undo("relabel", e);
-    }
-  }
-  if (scene->vnrm) (void)hipFree(scene->vnrm);
-  if (scene->vnrm4) (void)hipFree(scene->vnrm4);
-  scene->vnrm = a, scene->vnrm4 = a4;
-  ++scene->vn_epoch;  // the primary-hit records of any context are those of another scene now
-  ctx->prim_valid = false;
+  DevBuf a, a4;
+  MCPT_TRY(upload_attr("set_vertex_normals", scene, scene->vnrm, vn ? rec.data() : nullptr, kFlatNormals, a, a4));
+  commit_attr(ctx, scene, {{(void **)&scene->vnrm, &a}, {(void **)&scene->vnrm4, &a4}});
   return MCPT_OK;
 }
 
@@ -3404,114 +3431,40 @@ int smooth_scene(const mcpt_scene *scene, SmoothScene *out, int *on, int *device
 }  // namespace mcpt
 }  // extern "C++"
 
-// tri4-ordered texture records from the reference-ordered ones (k_vnrm_relabel's
-// rule): an empty slot or a foreign id gets the untextured record
-__global__ void __launch_bounds__(256) k_texrec_relabel(const DevTri *__restrict__ tri4, int64_t n4, int64_t n_tris,
-                                                        const TexRec *__restrict__ rec, TexRec *__restrict__ rec4) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= n4) return;
-  const int64_t t = (int64_t)mcpt::n96_bits(tri4[k].aux.y);
-  TexRec r;
-  r.q[0] = r.q[1] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-  if (t < n_tris) r = rec[t];
-  rec4[k] = r;
-}
+static_assert(sizeof(mcpt::TexRecHost) == sizeof(TexRec) && sizeof(mcpt::BumpRecHost) == sizeof(BumpRec) &&
+                  sizeof(mcpt::Quad) == sizeof(f4),
+              "mcpt_attr.h packs the records' and texels' bytes");
 
 int mcpt_scene_set_textures(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_textures *tx) {
-  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_textures: null context or scene");
-  if (ctx->device != scene->device)
-    return mcpt::fail(MCPT_ERR_ARG, "set_textures: scene and context are on different GPUs");
+  static const mcpt::AttrNames names = {"set_textures", "texture"};
+  MCPT_TRY(check_handles(names.who, ctx, scene));
   HIP_OK(hipSetDevice(scene->device));
   const int64_t n = scene->n_tris;
   // validate everything before anything changes: a failed call leaves the scene's textures as they were
-  std::vector<TexRec> rec;
-  std::vector<f4> pool;
-  std::vector<int64_t> dims_base;  // each texture's first texel in the pool
+  std::vector<mcpt::TexRecHost> rec;
+  std::vector<mcpt::Quad> pool;
+  std::vector<int64_t> base;  // each texture's first texel in the pool
   if (tx) {
     if (!tx->uv || !tx->tri_tex || tx->n_textures < 0 || (tx->n_textures > 0 && !tx->images))
       return mcpt::fail(MCPT_ERR_ARG, "set_textures: null uv, tri_tex or images");
-    std::vector<int64_t> &base = dims_base;
-    base.resize((size_t)tx->n_textures);
     int64_t total = 0;
-    for (int32_t k = 0; k < tx->n_textures; ++k) {
-      const mcpt_texture_image &im = tx->images[k];
-      if (!im.rgb || im.width < 1 || im.width > 16384 || im.height < 1 || im.height > 16384)
-        return mcpt::fail(MCPT_ERR_ARG, "set_textures: texture " + std::to_string(k) + " has no texels or a side outside 1..16384");
-      base[(size_t)k] = total;
-      total += (int64_t)im.width * im.height;
-      if (total > (1ll << 27)) return mcpt::fail(MCPT_ERR_ARG, "set_textures: more than 2^27 texels in all");
-    }
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t t = tx->tri_tex[i];
-      if (t < -1 || t >= tx->n_textures)
-        return mcpt::fail(MCPT_ERR_ARG, "set_textures: texture index out of range (triangle " + std::to_string(i) + ")");
-      for (int k = 0; k < 6 && t >= 0; ++k)
-        if (!(std::fabs(tx->uv[6 * i + k]) <= 1048576.0f))
-          return mcpt::fail(MCPT_ERR_ARG, "set_textures: a texture coordinate is not finite or beyond 2^20 (triangle " +
-                                              std::to_string(i) + ")");
-    }
-    pool.resize((size_t)std::max<int64_t>(total, 1));
-    pool[0] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-    for (int32_t k = 0; k < tx->n_textures; ++k) {
-      const mcpt_texture_image &im = tx->images[k];
-      const int64_t m = (int64_t)im.width * im.height;
-      for (int64_t j = 0; j < m; ++j) {
-        const float r = im.rgb[3 * j], g = im.rgb[3 * j + 1], b = im.rgb[3 * j + 2];
-        if (!(r >= 0.0f && r < INFINITY && g >= 0.0f && g < INFINITY && b >= 0.0f && b < INFINITY))
-          return mcpt::fail(MCPT_ERR_ARG, "set_textures: texture " + std::to_string(k) + " has a negative or non-finite texel");
-        pool[(size_t)(base[(size_t)k] + j)] = (f4){r, g, b, 1.0f};  // opaque until an alpha is set
-      }
-    }
-    rec.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-      TexRec &r = rec[(size_t)i];
-      r.q[0] = r.q[1] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-      const int32_t t = tx->tri_tex[i];
-      if (t < 0) continue;
-      const mcpt_texture_image &im = tx->images[t];
-      const float *u = tx->uv + 6 * i;
-      const uint32_t off = (uint32_t)base[(size_t)t], size = (uint32_t)im.width | ((uint32_t)im.height << 16);
-      r.q[0] = (f4){__builtin_bit_cast(float, off), __builtin_bit_cast(float, size), u[0], u[1]};
-      r.q[1] = (f4){u[2], u[3], u[4], u[5]};
-    }
+    std::string bad = mcpt::pool_layout(names, tx->images, tx->n_textures, &mcpt_texture_image::rgb, base, &total);
+    if (bad.empty()) bad = mcpt::check_index_uv(names, tx->tri_tex, tx->uv, n, tx->n_textures);
+    if (bad.empty())
+      bad = mcpt::pack_pool(names, tx->images, tx->n_textures, &mcpt_texture_image::rgb, base, total, {0.0f, 0.0f, 0.0f, 0.0f},
+                            mcpt::texture_texel, "has a negative or non-finite texel", pool);
+    if (!bad.empty()) return mcpt::fail(MCPT_ERR_ARG, bad);
+    rec = mcpt::pack_tex_records(tx->images, base, tx->tri_tex, tx->uv, n);
   }
-  // renders already enqueued may still read the previous arrays: wait for them
-  if (scene->texrec) HIP_OK(hipDeviceSynchronize());
-  TexRec *a = nullptr, *a4 = nullptr;
-  f4 *px = nullptr;
-  if (tx) {
-    auto undo = [&](const std::string &what, hipError_t e) {
-      for (void *p : {(void *)a, (void *)a4, (void *)px})
-        if (p) (void)hipFree(p);
-      return mcpt::fail(MCPT_ERR_HIP, "set_textures: " + what + ": " + hipGetErrorString(e));
-    };
-    hipError_t e = hipMalloc((void **)&a, (size_t)std::max<int64_t>(n, 1) * sizeof(TexRec));
-    if (e != hipSuccess) return a = nullptr, undo("allocation", e);
-    e = hipMemcpy(a, rec.data(), (size_t)n * sizeof(TexRec), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return undo("upload", e);
-    e = hipMalloc((void **)&px, pool.size() * sizeof(f4));
-    if (e != hipSuccess) return px = nullptr, undo("allocation", e);
-    e = hipMemcpy(px, pool.data(), pool.size() * sizeof(f4), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return undo("upload", e);
-    if (scene->tri4) {
-      const int64_t n4 = 4 * (int64_t)scene->view.n_near4;
-      e = hipMalloc((void **)&a4, (size_t)n4 * sizeof(TexRec));
-      if (e != hipSuccess) return a4 = nullptr, undo("allocation", e);
-      hipLaunchKernelGGL(k_texrec_relabel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, scene->tri4, n4, n, a, a4);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) return undo("relabel", e);
-    }
-  }
-  for (void *p : {(void *)scene->texrec, (void *)scene->texrec4, (void *)scene->texels})
-    if (p) (void)hipFree(p);
-  scene->texrec = a, scene->texrec4 = a4, scene->texels = px, scene->n_texels = tx ? (int64_t)pool.size() : 0;
+  DevBuf a, a4, px;
+  MCPT_TRY(upload_attr("set_textures", scene, scene->texrec, tx ? rec.data() : nullptr, TexRec{}, a, a4));
+  if (tx) MCPT_TRY(upload_bytes("set_textures", px, pool.data(), pool.size() * sizeof(f4)));
+  commit_attr(ctx, scene, {{(void **)&scene->texrec, &a}, {(void **)&scene->texrec4, &a4}, {(void **)&scene->texels, &px}});
+  scene->n_texels = tx ? (int64_t)pool.size() : 0;
   scene->cut_a0 = 0.0f;  // a new texture set (or none) has no alpha
   scene->tex_dims.clear();
   for (int32_t k = 0; tx && k < tx->n_textures; ++k)
-    scene->tex_dims.push_back({dims_base[(size_t)k], (int64_t)tx->images[k].width, (int64_t)tx->images[k].height});
-  ++scene->vn_epoch;  // the primary-hit records of any context are those of another scene now
-  ctx->prim_valid = false;
+    scene->tex_dims.push_back({base[(size_t)k], (int64_t)tx->images[k].width, (int64_t)tx->images[k].height});
   return MCPT_OK;
 }
 
@@ -3523,9 +3476,7 @@ __global__ void __launch_bounds__(256) k_set_texel_alpha(f4 *__restrict__ texels
 }
 
 int mcpt_scene_set_texture_alpha(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_texture_alpha *al) {
-  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: null context or scene");
-  if (ctx->device != scene->device)
-    return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: scene and context are on different GPUs");
+  MCPT_TRY(check_handles("set_texture_alpha", ctx, scene));
   if (!scene->texrec) return mcpt::fail(MCPT_ERR_ARG, "set_texture_alpha: the scene has no textures");
   // validate everything before anything changes: a failed call leaves the scene as it was
   const int64_t total = scene->n_texels;
@@ -3550,15 +3501,15 @@ int mcpt_scene_set_texture_alpha(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_te
   }
   HIP_OK(hipSetDevice(scene->device));
   HIP_OK(hipDeviceSynchronize());  // renders already enqueued may still read the texels
-  float *dw = nullptr;
-  HIP_OK(hipMalloc((void **)&dw, (size_t)total * sizeof(float)));
-  hipError_t e = hipMemcpy(dw, w.data(), (size_t)total * sizeof(float), hipMemcpyHostToDevice);
+  DevBuf dw;
+  HIP_OK(dw.alloc((size_t)total * sizeof(float)));
+  hipError_t e = hipMemcpy(dw.p, w.data(), (size_t)total * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_set_texel_alpha, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, scene->texels, dw, total);
+    hipLaunchKernelGGL(k_set_texel_alpha, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, scene->texels,
+                       (const float *)dw.p, total);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
   }
-  (void)hipFree(dw);
   if (e != hipSuccess) return mcpt::fail(MCPT_ERR_HIP, std::string("set_texture_alpha: ") + hipGetErrorString(e));
   scene->cut_a0 = al ? al->threshold : 0.0f;
   ++scene->vn_epoch;  // the primary-hit records hold the factor's .w: they are another scene's now
@@ -3578,128 +3529,35 @@ int texture_scene(const mcpt_scene *scene, TextureScene *out, int *on, int *devi
 }  // namespace mcpt
 }  // extern "C++"
 
-// tri4-ordered normal-map records from the reference-ordered ones
-// (k_texrec_relabel's rule): an empty slot or a foreign id gets the unmapped record
-__global__ void __launch_bounds__(256) k_bumprec_relabel(const DevTri *__restrict__ tri4, int64_t n4, int64_t n_tris,
-                                                         const BumpRec *__restrict__ rec, BumpRec *__restrict__ rec4) {
-  const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (k >= n4) return;
-  const int64_t t = (int64_t)mcpt::n96_bits(tri4[k].aux.y);
-  BumpRec r;
-  r.q[0] = r.q[1] = r.q[2] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-  if (t < n_tris) r = rec[t];
-  rec4[k] = r;
-}
-
 int mcpt_scene_set_normal_maps(mcpt_ctx *ctx, mcpt_scene *scene, const mcpt_normal_maps *nm) {
-  if (!ctx || !scene) return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: null context or scene");
-  if (ctx->device != scene->device)
-    return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: scene and context are on different GPUs");
+  static const mcpt::AttrNames names = {"set_normal_maps", "map"};
+  MCPT_TRY(check_handles(names.who, ctx, scene));
   HIP_OK(hipSetDevice(scene->device));
   const int64_t n = scene->n_tris;
   // validate everything before anything changes: a failed call leaves the scene's maps as they were
-  std::vector<BumpRec> rec;
-  std::vector<f4> pool;
+  std::vector<mcpt::BumpRecHost> rec;
+  std::vector<mcpt::Quad> pool;
   if (nm) {
     if (!nm->uv || !nm->tri_map || nm->n_maps < 0 || (nm->n_maps > 0 && !nm->images))
       return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: null uv, tri_map or images");
-    std::vector<int64_t> base((size_t)nm->n_maps);
+    std::vector<int64_t> base;
     int64_t total = 0;
-    for (int32_t k = 0; k < nm->n_maps; ++k) {  // the sizes alone, before a texel is read
-      const mcpt_normal_map_image &im = nm->images[k];
-      if (!im.xyz || im.width < 1 || im.width > 16384 || im.height < 1 || im.height > 16384)
-        return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: map " + std::to_string(k) + " has no texels or a side outside 1..16384");
-      base[(size_t)k] = total;
-      total += (int64_t)im.width * im.height;
-      if (total > (1ll << 27)) return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: more than 2^27 texels in all");
-    }
-    for (int64_t i = 0; i < n; ++i) {
-      const int32_t t = nm->tri_map[i];
-      if (t < -1 || t >= nm->n_maps)
-        return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: map index out of range (triangle " + std::to_string(i) + ")");
-      for (int k = 0; k < 6 && t >= 0; ++k)
-        if (!(std::fabs(nm->uv[6 * i + k]) <= 1048576.0f))
-          return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: a texture coordinate is not finite or beyond 2^20 (triangle " +
-                                              std::to_string(i) + ")");
-    }
-    pool.resize((size_t)std::max<int64_t>(total, 1));
-    pool[0] = (f4){0.0f, 0.0f, 1.0f, 0.0f};
-    for (int32_t k = 0; k < nm->n_maps; ++k) {
-      const mcpt_normal_map_image &im = nm->images[k];
-      const int64_t m = (int64_t)im.width * im.height;
-      for (int64_t j = 0; j < m; ++j) {
-        const float x = im.xyz[3 * j], y = im.xyz[3 * j + 1], z = im.xyz[3 * j + 2];
-        const double len = std::sqrt((double)x * x + (double)y * y + (double)z * z);
-        if (!(std::fabs(len - 1.0) <= 1e-3 && z > 0.0f))
-          return mcpt::fail(MCPT_ERR_ARG, "set_normal_maps: map " + std::to_string(k) + " has a texel that is not unit or has z <= 0");
-        pool[(size_t)(base[(size_t)k] + j)] = (f4){x, y, z, 0.0f};
-      }
-    }
-    // the tangent frame per triangle, in double from the uploaded rows (v0, nab
-    // = -(v1 - v0), nac = -(v2 - v0), the packed face normal in their .w lanes)
+    std::string bad = mcpt::pool_layout(names, nm->images, nm->n_maps, &mcpt_normal_map_image::xyz, base, &total);
+    if (bad.empty()) bad = mcpt::check_index_uv(names, nm->tri_map, nm->uv, n, nm->n_maps);
+    if (bad.empty())
+      bad = mcpt::pack_pool(names, nm->images, nm->n_maps, &mcpt_normal_map_image::xyz, base, total, {0.0f, 0.0f, 1.0f, 0.0f},
+                            mcpt::normal_map_texel, "has a texel that is not unit or has z <= 0", pool);
+    if (!bad.empty()) return mcpt::fail(MCPT_ERR_ARG, bad);
+    // the tangent frames come from the uploaded triangle rows
     std::vector<DevTri> tris((size_t)n);
-    if (n > 0) HIP_OK(hipMemcpy(tris.data(), scene->tris, (size_t)n * sizeof(DevTri), hipMemcpyDeviceToHost));
-    rec.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-      BumpRec &r = rec[(size_t)i];
-      r.q[0] = r.q[1] = r.q[2] = (f4){0.0f, 0.0f, 0.0f, 0.0f};
-      const int32_t t = nm->tri_map[i];
-      if (t < 0) continue;
-      const mcpt_normal_map_image &im = nm->images[t];
-      const float *u = nm->uv + 6 * i;
-      const DevTri &T = tris[(size_t)i];
-      const double e1[3] = {-(double)T.nab.x, -(double)T.nab.y, -(double)T.nab.z};
-      const double e2[3] = {-(double)T.nac.x, -(double)T.nac.y, -(double)T.nac.z};
-      const double ng[3] = {T.v0.w, T.nab.w, T.nac.w};
-      const double du1 = (double)u[2] - u[0], dv1 = (double)u[3] - u[1];
-      const double du2 = (double)u[4] - u[0], dv2 = (double)u[5] - u[1];
-      const double det = du1 * dv2 - du2 * dv1;
-      if (!(det != 0.0 && std::isfinite(det))) continue;  // degenerate UVs: unmapped
-      double Tn[3], Bn[3];
-      for (int k = 0; k < 3; ++k) Tn[k] = (dv2 * e1[k] - dv1 * e2[k]) / det, Bn[k] = (du1 * e2[k] - du2 * e1[k]) / det;
-      const double tl = std::sqrt(Tn[0] * Tn[0] + Tn[1] * Tn[1] + Tn[2] * Tn[2]);
-      if (!(tl > 0.0 && std::isfinite(tl))) continue;
-      const double c[3] = {ng[1] * Tn[2] - ng[2] * Tn[1], ng[2] * Tn[0] - ng[0] * Tn[2], ng[0] * Tn[1] - ng[1] * Tn[0]};
-      const float h = c[0] * Bn[0] + c[1] * Bn[1] + c[2] * Bn[2] >= 0.0 ? 1.0f : -1.0f;
-      const uint32_t off = (uint32_t)base[(size_t)t], size = (uint32_t)im.width | ((uint32_t)im.height << 16);
-      r.q[0] = (f4){__builtin_bit_cast(float, off), __builtin_bit_cast(float, size), u[0], u[1]};
-      r.q[1] = (f4){u[2], u[3], u[4], u[5]};
-      r.q[2] = (f4){(float)(Tn[0] / tl), (float)(Tn[1] / tl), (float)(Tn[2] / tl), h};
-    }
+    HIP_OK(hipMemcpy(tris.data(), scene->tris, (size_t)n * sizeof(DevTri), hipMemcpyDeviceToHost));
+    rec = mcpt::pack_bump_records(nm->images, base, nm->tri_map, nm->uv, reinterpret_cast<const float *>(tris.data()), n);
   }
-  // renders already enqueued may still read the previous arrays: wait for them
-  if (scene->bumprec) HIP_OK(hipDeviceSynchronize());
-  BumpRec *a = nullptr, *a4 = nullptr;
-  f4 *px = nullptr;
-  if (nm) {
-    auto undo = [&](const std::string &what, hipError_t e) {
-      for (void *p : {(void *)a, (void *)a4, (void *)px})
-        if (p) (void)hipFree(p);
-      return mcpt::fail(MCPT_ERR_HIP, "set_normal_maps: " + what + ": " + hipGetErrorString(e));
-    };
-    hipError_t e = hipMalloc((void **)&a, (size_t)std::max<int64_t>(n, 1) * sizeof(BumpRec));
-    if (e != hipSuccess) return a = nullptr, undo("allocation", e);
-    e = hipMemcpy(a, rec.data(), (size_t)n * sizeof(BumpRec), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return undo("upload", e);
-    e = hipMalloc((void **)&px, pool.size() * sizeof(f4));
-    if (e != hipSuccess) return px = nullptr, undo("allocation", e);
-    e = hipMemcpy(px, pool.data(), pool.size() * sizeof(f4), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return undo("upload", e);
-    if (scene->tri4) {
-      const int64_t n4 = 4 * (int64_t)scene->view.n_near4;
-      e = hipMalloc((void **)&a4, (size_t)n4 * sizeof(BumpRec));
-      if (e != hipSuccess) return a4 = nullptr, undo("allocation", e);
-      hipLaunchKernelGGL(k_bumprec_relabel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, nullptr, scene->tri4, n4, n, a, a4);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) return undo("relabel", e);
-    }
-  }
-  for (void *p : {(void *)scene->bumprec, (void *)scene->bumprec4, (void *)scene->bump_texels})
-    if (p) (void)hipFree(p);
-  scene->bumprec = a, scene->bumprec4 = a4, scene->bump_texels = px, scene->n_bump_texels = nm ? (int64_t)pool.size() : 0;
-  ++scene->vn_epoch;  // the primary-hit records of any context are those of another scene now
-  ctx->prim_valid = false;
+  DevBuf a, a4, px;
+  MCPT_TRY(upload_attr("set_normal_maps", scene, scene->bumprec, nm ? rec.data() : nullptr, BumpRec{}, a, a4));
+  if (nm) MCPT_TRY(upload_bytes("set_normal_maps", px, pool.data(), pool.size() * sizeof(f4)));
+  commit_attr(ctx, scene, {{(void **)&scene->bumprec, &a}, {(void **)&scene->bumprec4, &a4}, {(void **)&scene->bump_texels, &px}});
+  scene->n_bump_texels = nm ? (int64_t)pool.size() : 0;
   return MCPT_OK;
 }
 
@@ -3714,6 +3572,11 @@ int bump_scene(const mcpt_scene *scene, BumpScene *out, int *on, int *device) {
 }
 }  // namespace mcpt
 }  // extern "C++"
+
+// What a scene's hits are shaded with, each level on top of the one below whether or not that one is
+// set: 0 the face normal and the material's kd (the reference), 1 vertex normals, 2 textures, 3 normal
+// maps.  The kernels of a level are compiled for it alone; the [level][NOPRUNE] tables below pick them.
+static int scene_level(const mcpt_scene *scene) { return scene->bumprec ? 3 : (scene->texrec ? 2 : (scene->vnrm ? 1 : 0)); }
 
 // The k_render instantiation of a render call and what it runs with.
 struct KernelChoice {
@@ -3795,14 +3658,12 @@ static int select_kernel(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rend
   // a scene with vertex normals: the N forms (smooth_render_fn), one shading form for any materials
   // a scene with textures: the textured forms on top of them (texture_render_fn), vertex normals or not
   // a scene with normal maps: the mapped forms on top of those (bump_render_fn), textures or not
-  const bool smooth = scene->vnrm != nullptr, textured = scene->texrec != nullptr, mapped = scene->bumprec != nullptr;
+  static const void *(*const level_fn[4])(int, int, int, int, int, int) = {nullptr, smooth_render_fn, texture_render_fn,
+                                                                           bump_render_fn};
+  const int level = scene_level(scene);
   auto fn_of = [&](int win_) {
-    if (mapped)
-      return bump_render_fn(kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0);
-    if (textured)
-      return texture_render_fn(kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0);
-    return smooth ? smooth_render_fn(kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0)
-                  : fns[win_][pair][glossy];
+    return level ? level_fn[level](kind, ctx->stats_on ? 1 : 0, win_, pair ? 1 : 0, p->jitter, scene->env_on ? 1 : 0)
+                 : fns[win_][pair][glossy];
   };
   // stack_window 1 forces the window (tests, experiments) even when the whole stack fits in it, 2 forbids it
   const bool forced = T.stack_window == 1;
@@ -3874,31 +3735,33 @@ static int primary_pass(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_rende
   // the pass writes its own stripes' costs only: zero the others, so
   // the tile keys and mcpt_get_primary_cost never read stale words
   if (p->stripe_count > 1) HIP_OK(hipMemsetAsync(ctx->d_prim_cost, 0, (size_t)n_px * sizeof(uint32_t), st));
-  if (scene->texrec || scene->bumprec) MCPT_TRY(grow_dev(ctx->prim_tex_cap, n_px, (void **)&ctx->d_prim_tex, sizeof(f4)));
-  if (scene->near4_bytes <= kPrimSmallTree || scene->vnrm || scene->texrec || scene->bumprec) {
+  const int level = scene_level(scene);
+  if (level >= 2) MCPT_TRY(grow_dev(ctx->prim_tex_cap, n_px, (void **)&ctx->d_prim_tex, sizeof(f4)));
+  if (scene->near4_bytes <= kPrimSmallTree || level > 0) {
     // small trees: one ray per lane, one 8x8 tile per workgroup; a scene with
     // vertex normals or textures at any size (the records then hold shading
     // normals and come with texture factors, which k_render's PRIM form does
     // not compute)
     const size_t lds_p = (size_t)K.depth_entries * 64 * sizeof(int32_t);
-    const dim3 g((unsigned)P.tiles);
-    if (scene->bumprec && p->mode == MCPT_MODE_NOPRUNE)  // normal maps: the record holds the mapped normal
-      hipLaunchKernelGGL(k_primary_bump<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
-    else if (scene->bumprec)
-      hipLaunchKernelGGL(k_primary_bump<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
-    else if (scene->texrec && p->mode == MCPT_MODE_NOPRUNE)
-      hipLaunchKernelGGL(k_primary_tex<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
-    else if (scene->texrec)
-      hipLaunchKernelGGL(k_primary_tex<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim, ctx->d_prim_tex);
-    else if (scene->vnrm && p->mode == MCPT_MODE_NOPRUNE)
-      hipLaunchKernelGGL((k_primary<MCPT_MODE_NOPRUNE, true>), g, dim3(64), lds_p, st, A, ctx->d_prim);
-    else if (scene->vnrm)
-      hipLaunchKernelGGL((k_primary<MCPT_MODE_EXACT, true>), g, dim3(64), lds_p, st, A, ctx->d_prim);
-    else if (p->mode == MCPT_MODE_NOPRUNE)
-      hipLaunchKernelGGL(k_primary<MCPT_MODE_NOPRUNE>, g, dim3(64), lds_p, st, A, ctx->d_prim);
-    else
-      hipLaunchKernelGGL(k_primary<MCPT_MODE_EXACT>, g, dim3(64), lds_p, st, A, ctx->d_prim);
-    HIP_OK(hipGetLastError());
+    // [level][NOPRUNE]: with vertex normals the record holds the shading normal, with normal maps the
+    // mapped one; the textured and mapped forms write the texture factors too (their third argument)
+    static const void *const kprim[4][2] = {
+        {(const void *)k_primary<MCPT_MODE_EXACT>, (const void *)k_primary<MCPT_MODE_NOPRUNE>},
+        {(const void *)k_primary<MCPT_MODE_EXACT, true>, (const void *)k_primary<MCPT_MODE_NOPRUNE, true>},
+        {(const void *)k_primary_tex<MCPT_MODE_EXACT>, (const void *)k_primary_tex<MCPT_MODE_NOPRUNE>},
+        {(const void *)k_primary_bump<MCPT_MODE_EXACT>, (const void *)k_primary_bump<MCPT_MODE_NOPRUNE>}};
+    // one argument list for the four: a form reads as many entries as it has parameters, so each form's
+    // parameter list must be a prefix of it
+    using Prim2 = void (*)(RenderArgs, PrimHit *);
+    using Prim3 = void (*)(RenderArgs, PrimHit *, f4 *);
+    static_assert(std::is_same_v<decltype(&k_primary<MCPT_MODE_EXACT>), Prim2> &&
+                      std::is_same_v<decltype(&k_primary<MCPT_MODE_NOPRUNE, true>), Prim2> &&
+                      std::is_same_v<decltype(&k_primary_tex<MCPT_MODE_EXACT>), Prim3> &&
+                      std::is_same_v<decltype(&k_primary_bump<MCPT_MODE_EXACT>), Prim3> &&
+                      std::is_same_v<decltype(ctx->d_prim), PrimHit *> && std::is_same_v<decltype(ctx->d_prim_tex), f4 *>,
+                  "kargs below is what every k_primary form takes");
+    void *kargs[] = {&A, &ctx->d_prim, &ctx->d_prim_tex};
+    HIP_OK(hipLaunchKernel(kprim[level][p->mode == MCPT_MODE_NOPRUNE], dim3((unsigned)P.tiles), dim3(64), kargs, lds_p, st));
     return MCPT_OK;
   }
   // the same persistent machine in its PRIM form: one frame, no state;
@@ -4254,33 +4117,31 @@ int mcpt_intersect(mcpt_ctx *ctx, const mcpt_scene *scene, const mcpt_ray *rays,
   // EXACT: a ray with a denormal direction component takes the literal search, on the binary tree's stack
   size_t lds = (size_t)(mode == MCPT_MODE_NOPRUNE ? scene->stack_depth : std::max(scene->stack_depth, scene->stack_depth4)) *
                64 * sizeof(int32_t);
-  dim3 g((unsigned)((n + 63) / 64));
-  const BumpView bv{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
-  if (scene->bumprec && mode == MCPT_MODE_NOPRUNE)  // normal maps: mcpt_hit.normal is the mapped normal
-    hipLaunchKernelGGL(k_intersect_bump<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin, scene->vnrm, bv);
-  else if (scene->bumprec)
-    hipLaunchKernelGGL(k_intersect_bump<MCPT_MODE_EXACT>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin, scene->vnrm, bv);
-  else if (scene->texrec && mode == MCPT_MODE_NOPRUNE)  // textures: triangle_id is the closest hit's triangle
-    hipLaunchKernelGGL(k_intersect_tex<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin, scene->vnrm);
-  else if (scene->texrec)
-    hipLaunchKernelGGL(k_intersect_tex<MCPT_MODE_EXACT>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin, scene->vnrm);
-  else if (scene->vnrm && mode == MCPT_MODE_NOPRUNE)  // vertex normals: mcpt_hit.normal is the shading normal
-    hipLaunchKernelGGL(k_intersect_smooth<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin, scene->vnrm);
-  else if (scene->vnrm)
-    hipLaunchKernelGGL(k_intersect_smooth<MCPT_MODE_EXACT>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin, scene->vnrm);
-  else if (mode == MCPT_MODE_NOPRUNE)
-    hipLaunchKernelGGL(k_intersect<MCPT_MODE_NOPRUNE>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin);
-  else
-    hipLaunchKernelGGL(k_intersect<MCPT_MODE_EXACT>, g, dim3(64), lds, (hipStream_t)stream, scene->view, rays, n,
-                       hits, tmin);
-  HIP_OK(hipGetLastError());
+  // [level][NOPRUNE]: with vertex normals mcpt_hit.normal is the shading normal, with textures triangle_id
+  // is the closest hit's triangle, with normal maps the normal is the mapped one
+  static const void *const kfns[4][2] = {
+      {(const void *)k_intersect<MCPT_MODE_EXACT>, (const void *)k_intersect<MCPT_MODE_NOPRUNE>},
+      {(const void *)k_intersect_smooth<MCPT_MODE_EXACT>, (const void *)k_intersect_smooth<MCPT_MODE_NOPRUNE>},
+      {(const void *)k_intersect_tex<MCPT_MODE_EXACT>, (const void *)k_intersect_tex<MCPT_MODE_NOPRUNE>},
+      {(const void *)k_intersect_bump<MCPT_MODE_EXACT>, (const void *)k_intersect_bump<MCPT_MODE_NOPRUNE>}};
+  SceneView view = scene->view;
+  const VtxNormals *vnrm = scene->vnrm;
+  BumpView bv{scene->bumprec, scene->bump_texels, scene->n_bump_texels};
+  // one argument list for the four: a form reads as many entries as it has parameters, so each form's
+  // parameter list must be a prefix of it
+  using Isect5 = void (*)(SceneView, const mcpt_ray *, int64_t, mcpt_hit *, float);
+  using Isect6 = void (*)(SceneView, const mcpt_ray *, int64_t, mcpt_hit *, float, const VtxNormals *);
+  using Isect7 = void (*)(SceneView, const mcpt_ray *, int64_t, mcpt_hit *, float, const VtxNormals *, BumpView);
+  static_assert(std::is_same_v<decltype(&k_intersect<MCPT_MODE_EXACT>), Isect5> &&
+                    std::is_same_v<decltype(&k_intersect_smooth<MCPT_MODE_EXACT>), Isect6> &&
+                    std::is_same_v<decltype(&k_intersect_tex<MCPT_MODE_EXACT>), Isect6> &&
+                    std::is_same_v<decltype(&k_intersect_bump<MCPT_MODE_EXACT>), Isect7> &&
+                    std::is_same_v<decltype(rays), const mcpt_ray *> && std::is_same_v<decltype(n), int64_t> &&
+                    std::is_same_v<decltype(hits), mcpt_hit *> && std::is_same_v<decltype(tmin), float>,
+                "kargs below is what every k_intersect form takes");
+  void *kargs[] = {&view, &rays, &n, &hits, &tmin, &vnrm, &bv};
+  HIP_OK(hipLaunchKernel(kfns[scene_level(scene)][mode == MCPT_MODE_NOPRUNE], dim3((unsigned)((n + 63) / 64)), dim3(64),
+                         kargs, lds, (hipStream_t)stream));
   return MCPT_OK;
 }
 

@@ -342,6 +342,51 @@ def test_primary_cache_is_dropped_by_set_and_clear(rnd, chain_ref):
         plain.close()
 
 
+def test_replacing_each_attribute_keeps_both_orderings_in_step(rnd, chain_ref):
+    """One scene on the 96-B nodes, whose launches read the tri4-ordered arrays
+    (vnrm4, texrec4, bumprec4), against the chain, whose kernels read the
+    reference-ordered ones: all three attributes set, each replaced by another
+    valid set, one cleared and set again.  After every step the two must give
+    the same bits, which they do not when a set frees, keeps or swaps the wrong
+    array of a pair."""
+    w, h, frames = 20, 13, 2
+    data, cam = scenes.cbox(), S.parse_camera(scenes.CBOX_CAM)
+    n = len(data.tris)
+    rng = np.random.Generator(np.random.PCG64(7))
+    uv, tri_tex, images = BC.cbox_textures()
+    # (two images on every triangle: the few lit paths of an image this small meet none of the first set's)
+    other_textures = (uv[:, ::-1].copy(), (np.arange(n) % 2).astype(np.int32),
+                      [rng.uniform(0.1, 1.0, (2, 7, 3)).astype(np.float32), rng.uniform(0.1, 1.0, (4, 3, 3)).astype(np.float32)])
+    # (a crease of 100 degrees rounds the boxes' right-angled edges, which 40 leaves sharp)
+    steps = [("normals replaced", lambda d: rnd.set_vertex_normals(d, S.vertex_normals(data.tris, 100.0))),
+             ("textures replaced", lambda d: rnd.set_textures(d, *other_textures)),
+             ("maps replaced", lambda d: rnd.set_normal_maps(d, *BC.cbox_maps(tilt=20.0))),
+             ("textures cleared", lambda d: rnd.clear_textures(d)),
+             ("textures set again", lambda d: rnd.set_textures(d, uv, tri_tex, images))]
+    dsc = rnd.upload(data)
+    seen = []
+    try:
+        rnd.set_tuning(quantized=3)
+        rnd.set_normal_maps(dsc, *BC.cbox_maps())
+        rnd.set_vertex_normals(dsc, S.vertex_normals(data.tris, 40.0))
+        rnd.set_textures(dsc, uv, tri_tex, images)
+        got = render(rnd, dsc, cam, w=w, h=h, frames=frames)
+        assert rnd.stats()["node_format"] == 2
+        assert_state_equal(got, chain_ref("both", w=w, h=h, frames=frames), "all three set")
+        seen.append(got[0].tobytes())
+        for what, step in steps:
+            step(dsc)
+            ref = BC.chain(rnd, dsc, cam, w, h, DEPTH, ATT, frames, R.default_seeds(w * h))
+            got = render(rnd, dsc, cam, w=w, h=h, frames=frames)
+            assert rnd.stats()["node_format"] == 2
+            assert_state_equal(got, ref, what)
+            assert got[0].tobytes() not in seen, what  # not vacuous: every step changes the image
+            seen.append(got[0].tobytes())
+    finally:
+        rnd.set_tuning()
+        dsc.close()
+
+
 def test_mapped_render_with_counters_on(rnd, boxes, chain_ref):
     dsc, cam = boxes("maps")
     try:

@@ -88,6 +88,24 @@ def test_texture_host_code_under_address_sanitizer(tmp_path):
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
 
 
+def test_attribute_host_code_under_address_sanitizer(tmp_path):
+    """The host half of mcpt_scene_set_textures and mcpt_scene_set_normal_maps
+    (csrc/mcpt_attr.h, a header without HIP) in a stand-alone program built here
+    with -fsanitize=address,undefined: every input the setters reject, with its
+    message, and a valid two-triangle, two-image set whose records are compared
+    with the layouts of mcpt_texture.h and mcpt_bump.h, every buffer a heap
+    block of exactly its size (tests/native/attr_check.cpp)."""
+    exe = str(tmp_path / "attr_asan")
+    cc = subprocess.run([os.environ.get("CXX", "g++"), "-O1", "-g", "-std=c++17", "-Wall", "-fno-omit-frame-pointer",
+                         "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
+                         os.path.join(ROOT, "tests", "native", "attr_check.cpp")], capture_output=True, text=True, timeout=300)
+    assert cc.returncode == 0, cc.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and r.stdout.strip().endswith("0 failures"), r.stdout[-2000:] + r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+
+
 # ------------------------------------------------------------------------ PNG
 def _png(w, h, ctype, rows, filters, palette=None, depth=8, interlace=0):
     """A PNG built here: rows = h byte strings of unfiltered pixels, each
